@@ -9,12 +9,17 @@ BASELINE.json headline workload (synthetic MSA, L=300, q=21, N=50 000).
 A "step" is one L-BFGS iteration of the fit as the library runs it by default (variable projection:
 every trial evaluation = forward GEMM, Newton solve of the fields, residual pass, backward GEMM, assemble;
 line-search evaluations and the two-loop recursion included) on the alignment already resident in HBM.  W warm-up iterations are followed by
-exactly K timed iterations, bracketed by barrier + device synchronise; rank 0 prints one
-JSON line.  With N > 1 the sites of the ONE problem -- and with them the parameters, the gradient and the L-BFGS
+exactly K timed iterations, bracketed by barrier + device synchronise; a fit that converges before (~170 iterations at
+the headline) starts over from its start point with the clock stopped.  Rank 0 prints one JSON line.  With N > 1 the sites of the ONE problem -- and with them the parameters, the gradient and the L-BFGS
 state -- are sharded across the ranks (strong scaling); per evaluation two neighbour all-to-alls (coupling halo,
 gradient halo) and scalar all-reduces over RCCL (evcouplings_amd/dist.py).
 
-Extra blocks on the same line:
+    --dump-outputs DIR   after the timed steps, what they computed as DIR/<name>.npy (see dump_outputs); the inputs
+                         are the same from run to run with the same arguments, so two builds compare output for output
+    --full               also the extra blocks below, each a run of its own (one GPU); a plain run sets up, warms up,
+                         times the K steps, dumps if asked and prints the headline line only
+
+Extra blocks on the same line (--full):
   roofline      dominant kernel (HIP events inside the library, on the stream it launches on)
   cpu_baseline  the oracle's float32/OpenMP build timed on this host on a bounded sample
   value_plmc_unit   joint L-BFGS iterations/s: plmc's own unit (value counts variable-projection iterations)
@@ -131,6 +136,29 @@ def pmc_traffic_per_evaluation():
     return (sum(per.values()) if per else None), per
 
 
+COUPLING_SAMPLE = 4_000_000       # entries of the coupling block dump_outputs writes (float32: 16 MB)
+
+
+def dump_outputs(path, x, res, L, q):
+    """What a caller of the timed path receives after its last step, as float32 / float64 .npy files in `path`:
+      fields.npy            (L, q) float32   h_i(a) of the parameter vector x
+      couplings_sample.npy  float32          J entries of x at a fixed sample of positions (sorted, seed 0) when the
+                                             coupling block is longer than COUPLING_SAMPLE, else the whole block
+      iterations.npy        (K, 4) float64   per timed iteration: iteration number, |g|/max(1,|x|), objective, NLL
+      fx.npy                (1,) float64     objective at the returned x
+    The wall-clock column of the iteration table is left out: it differs from run to run."""
+    os.makedirs(path, exist_ok=True)
+    nf = L * q
+    J = x[nf:]
+    if J.size > COUPLING_SAMPLE:
+        J = J[np.sort(np.random.default_rng(0).choice(J.size, COUPLING_SAMPLE, replace=False))]
+    np.save(os.path.join(path, "fields.npy"), np.ascontiguousarray(x[:nf], dtype=np.float32).reshape(L, q))
+    np.save(os.path.join(path, "couplings_sample.npy"), np.ascontiguousarray(J, dtype=np.float32))
+    table = np.array([(r[0], r[2], r[3], r[4]) for r in res["table"]], dtype=np.float64).reshape(-1, 4)
+    np.save(os.path.join(path, "iterations.npy"), table)
+    np.save(os.path.join(path, "fx.npy"), np.array([res["fx"]], dtype=np.float64))
+
+
 def relaunch_under_torchrun(n_gpus, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks here (one per GPU, rendezvous on 127.0.0.1 --
     the container's hostname may not resolve) and hand their exit code back.  Rank 0 prints the JSON line."""
@@ -165,7 +193,14 @@ def main():
     ap.add_argument("--joint-fit-cap", type=int, default=300,
                     help="iteration cap of the joint L-BFGS leg (PLM_FLAG_JOINT_LBFGS, plmc's algorithm; 0 = skip)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the whole-fit legs and the CPU baseline (one GPU; --no-fit / --no-cpu "
+                         "leave legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed steps computed as DIR/<name>.npy (with N > 1 ranks: DIR/rank<r>/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch_under_torchrun(args.gpus, sys.argv[1:]))
@@ -209,7 +244,7 @@ def main():
     t_setup = time.time()
     native = False
     # epsilon = the production stop rule (it also selects the 24-bit residual planes; a fit asked to go below 1e-4 would
-    # run 32-bit ones): far from reachable within warm-up + timed iterations, asserted below
+    # run 32-bit ones).  The headline fit reaches it in ~170 iterations; a longer window starts the fit over (run_steps)
     ctx1 = plm.PlmContext(msa, q=q, lambda_h=0.01, lambda_j=lam_j, device=local_rank, max_iter=args.warmup,
                           epsilon=1e-3)
     w, counts, n_eff = ctx1.reweight()
@@ -251,19 +286,41 @@ def main():
         ctx._set_max_iter(k)
         return ctx.optimize()
 
+    def run_steps(k):
+        """Exactly k L-BFGS iterations from the current x; returns (result, seconds).  A fit that stops before k (at the
+        headline it converges after ~170) starts over from its start point -- the set-up's x, set outside the clock --
+        so that a step is always an iteration of the fit.  `seconds` covers the optimise calls only; `result` sums
+        iterations and evaluations and joins the iteration tables, its other entries are those of the last call."""
+        sync()
+        res, secs, restarted = None, 0.0, False
+        while res is None or res["iters"] < k:
+            if res is not None:
+                ctx.set_x(None if world == 1 else x0)
+                sync()
+                restarted = True
+            t = time.perf_counter()
+            r = run_iters(k - (res["iters"] if res else 0))
+            sync()
+            secs += time.perf_counter() - t
+            if r["iters"] == 0 and restarted:
+                raise SystemExit("the fit stopped at its start point: %s" % r["status_msg"])
+            if res is not None:
+                r.update(iters=res["iters"] + r["iters"], n_evals=res["n_evals"] + r["n_evals"],
+                         table=res["table"] + r["table"])
+            res = r
+        return res, secs
+
     if args.warmup > 0:
-        run_iters(args.warmup)
-    sync()
-    t0 = time.perf_counter()
-    res = run_iters(args.steps)
-    sync()
-    dt = time.perf_counter() - t0
-    solver = ctx.solver_stats()          # field solver of the timed window (HIP events inside the library)
+        run_steps(args.warmup)
+    res, dt = run_steps(args.steps)
     if dist is not None:
         tt = torch.tensor([dt], device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert res["iters"] == args.steps, res
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     ctx.get_x(), res, L, q)
 
     out = {
         "metric": "plmc L-BFGS iterations/sec (PLM fit, synthetic MSA)",
@@ -300,8 +357,9 @@ def main():
                              "where the joint L-BFGS of round 1 (83 it/s) needed > 6000 -- see fit.*"},
     }
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # --- roofline of the dominant kernel (HIP events on the library's stream) ----------
+        solver = ctx.solver_stats()      # field solver of the timed window (HIP events inside the library)
         km = ctx.time_kernels(reps=5)
         # `fields`: what the field solver of an evaluation REALLY cost in the timed window (its whole chain of passes,
         # HIP events around it in every evaluation); time_kernels' own figure -- one Newton step + the residual pass --

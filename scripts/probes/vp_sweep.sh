@@ -3,7 +3,7 @@
 VAR=$1; shift
 for v in "$@"; do
   echo "== $VAR=$v"
-  env $VAR=$v python bench.py --no-cpu --joint-fit-cap 0 2>/dev/null | python -c "
+  env $VAR=$v python bench.py --full --no-cpu --joint-fit-cap 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline']['kernel_ms']

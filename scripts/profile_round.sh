@@ -1,14 +1,15 @@
 #!/bin/bash
-# profile_round.sh TAG: rocprofv3 kernel-trace statistics of the default bench command (CPU leg skipped: it launches
+# profile_round.sh TAG: rocprofv3 kernel-trace statistics of the full bench command (CPU leg skipped: it launches
 # no kernels) + the PMC passes (each counter set is its own run, never combined with trace domains other than
 # --kernel-trace); summaries left under gpurun_out/prof_TAG for copying into profiles/ (run through gpurun).
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r04}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- \
-    python $GRAFT_REPO_ROOT/bench.py --steps 30 --warmup 5 --no-cpu > $OUT/bench_under_rocprof.log 2>&1
+    python $ROOT/bench.py --full --steps 30 --warmup 5 --no-cpu > $OUT/bench_under_rocprof.log 2>&1
 echo "stats rc=$?"
 find $OUT/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
 i=0
