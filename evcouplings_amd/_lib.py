@@ -82,6 +82,10 @@ SYMBOLS = [
     ("plm_scores_ex", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("plm_hamiltonians", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int, _P, _P]),
     ("plm_potentials", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int, _P, _P]),
+    ("plm_model_pair_scores", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P, _P]),
+    ("plm_model_pair_scores_ex", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int, _P, _P, _P]),
+    ("plm_double_mutants", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),
+    ("plm_independent_fields", C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P, _P, _P]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),

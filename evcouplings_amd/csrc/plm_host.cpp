@@ -74,6 +74,11 @@ int check_device(int device) {
     return PLM_OK;
 }
 
+}  // namespace
+// device check of the entry points in the other translation units (plm_model.hip)
+int plm_check_device(int device) { return check_device(device); }
+namespace {
+
 // identity threshold of the reweighting: the integer rule, or what a float32 plmc makes of
 // the `-t 1-theta` that run_plmc sends it (tools.py:236-239)
 int cluster_threshold(double theta_id, int L, int conv) {

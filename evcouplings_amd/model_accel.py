@@ -9,10 +9,17 @@ module attributes to wrappers around libplm_hip (`plm_hamiltonians`, `plm_potent
 and return layouts are the reference's.  There is no CPU fallback: without the library the wrappers raise.
 `install(reader=True)` also swaps the class's plmc_v2 reader (L^2 tiny `np.fromfile` calls, model.py:364-389)
 for a block-wise one -- host-side format code, same attributes; measured to be no faster (see read_plmc_v2).
+`install(analysis=True)` also rebinds the numeric rest of the class (DESIGN_NEXT_ROWS.md section 9.5):
+`_calculate_ecs` (FN / MI / CN / the EC table), the `double_mut_mat` property and `to_independent_model`, on
+`plm_model_pair_scores`, `plm_double_mutants` and `plm_independent_fields`.  Off by default.
 """
+from copy import deepcopy
+
 import numpy as np
 
 _ORIGINAL = {}
+_ANALYSIS = {}                 # class -> {attribute name: the class's own attribute before install(analysis=True)}
+_ANALYSIS_NAMES = ("_calculate_ecs", "double_mut_mat", "to_independent_model")
 
 
 def _pairs_from_dense(J_ij):
@@ -75,10 +82,82 @@ def read_plmc_v2(self, f, precision):
         self.transform_from_plmc_model()
 
 
-def install(model_module=None, reader=False):
+def calculate_ecs(self):
+    """
+    Drop-in for `CouplingsModel._calculate_ecs` (model.py:777-827): FN of the zero-sum-gauged couplings and raw MI of
+    every pair from one kernel (plm_model_pair_scores), CN and MI-APC from the object's own `apc`, and the EC table with
+    the reference's columns, dtypes, row order (i < j, row-major, hence its index labels) and final
+    sort_values(by="cn", ascending=False).  seqdist is NaN when index_list is not numeric, as the reference's
+    try/except TypeError gives.
+    """
+    import pandas as pd
+    from evcouplings_amd import plm
+    fn, mi = plm.model_pair_scores(self.J_ij, self.f_ij, self.f_i)
+    self._fn_scores = fn
+    self._mi_scores_raw = mi
+    self._cn_scores = self.apc(fn)
+    self._mi_scores_apc = self.apc(mi)
+    iu, ju = np.triu_indices(self.L, 1)
+    index_list, target_seq = np.asarray(self.index_list), np.asarray(self.target_seq)
+    idx_i, idx_j = index_list[iu], index_list[ju]
+    try:
+        seqdist = np.abs(idx_i - idx_j)
+    except TypeError:
+        seqdist = np.full(len(iu), np.nan)
+    self._ecs = pd.DataFrame({
+        "i": idx_i, "A_i": target_seq[iu].astype(object), "j": idx_j, "A_j": target_seq[ju].astype(object),
+        "seqdist": seqdist, "mi_raw": mi[iu, ju], "mi_apc": self._mi_scores_apc[iu, ju],
+        "fn": fn[iu, ju], "cn": self._cn_scores[iu, ju],
+    }).sort_values(by="cn", ascending=False)
+
+
+def _double_mut_mat(self):
+    """
+    Drop-in for the `CouplingsModel.double_mut_mat` property (model.py:715-742): the L x L x q x q double-mutant
+    matrix of the target from plm_double_mutants, cached in `_double_mut_mat`.  Built on `self.single_mut_mat`,
+    whatever computes it, so it is consistent with the single-mutant matrix the caller sees.
+    """
+    if self._double_mut_mat is None:
+        from evcouplings_amd import plm
+        self._double_mut_mat = plm.double_mutant_matrix(self.J_ij, self.single_mut_mat, self.target_seq_mapped)
+    return self._double_mut_mat
+
+
+double_mut_mat = property(_double_mut_mat)
+
+
+def to_independent_model(self):
+    """
+    Drop-in for `CouplingsModel.to_independent_model` (model.py:882-927): the reference's deepcopy / h_i /
+    J_ij.fill(0) / _reset_precomputed sequence, with the per-site fmin_bfgs replaced by the exact minimiser of the same
+    objective (plm_independent_fields, Newton to |g|_inf <= 1e-12 max(1, N_eff)).  When lambda_h <= 0 the optimum need
+    not exist (a state with f_i = 0 drives its field to -inf), so the call goes to the original method, whose
+    iteration count bounds it.
+    """
+    if not float(self.lambda_h) > 0.0:
+        return _analysis_original(type(self), "to_independent_model")(self)
+    from evcouplings_amd import plm
+    h_i, _ = plm.independent_fields(self.f_i, self.lambda_h, self.N_eff)
+    c0 = deepcopy(self)
+    c0.h_i = h_i
+    c0.J_ij.fill(0)
+    c0._reset_precomputed()
+    return c0
+
+
+def _analysis_original(cls, name):
+    for k in cls.__mro__:
+        if k in _ANALYSIS and name in _ANALYSIS[k]:
+            return _ANALYSIS[k][name]
+    raise AttributeError("%s.%s: model_accel analysis drop-ins are not installed" % (cls.__name__, name))
+
+
+def install(model_module=None, reader=False, analysis=False):
     """
     Rebind, in evcouplings.couplings.model (or the module object given): the two Hamiltonian loops and,
-    if the module has a CouplingsModel class and `reader` is true, its plmc_v2 reader.
+    if the module has a CouplingsModel class and `reader` is true, its plmc_v2 reader; if `analysis` is true, the
+    class's `_calculate_ecs`, `double_mut_mat` and `to_independent_model` (subclasses such as
+    MeanFieldCouplingsModel reach them through super() or inheritance).  `uninstall()` restores all of them.
     """
     if model_module is None:
         import evcouplings.couplings.model as model_module
@@ -90,6 +169,12 @@ def install(model_module=None, reader=False):
     model_module._single_mutant_hamiltonians = single_mutant_hamiltonians
     if reader and cls is not None:
         setattr(cls, "_CouplingsModel__read_plmc_v2", read_plmc_v2)
+    if analysis and cls is not None:
+        if cls not in _ANALYSIS:
+            _ANALYSIS[cls] = {name: cls.__dict__[name] for name in _ANALYSIS_NAMES}
+        cls._calculate_ecs = calculate_ecs
+        cls.double_mut_mat = double_mut_mat
+        cls.to_independent_model = to_independent_model
     return model_module
 
 
@@ -102,3 +187,7 @@ def uninstall(model_module=None):
         cls = getattr(model_module, "CouplingsModel", None)
         if cls is not None and rd is not None:
             setattr(cls, "_CouplingsModel__read_plmc_v2", rd)
+    cls = getattr(model_module, "CouplingsModel", None)
+    if cls in _ANALYSIS:
+        for name, attr in _ANALYSIS.pop(cls).items():
+            setattr(cls, name, attr)

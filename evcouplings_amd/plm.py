@@ -218,6 +218,64 @@ def direct_information(jij_full, fi, device=0):
     return di
 
 
+# ---- analysis of a fitted model (the numeric rest of the reference's CouplingsModel) ----------------------------
+MODEL_FI_PRODUCT_F32 = 1
+
+
+def _f64(a):
+    """contiguous float64 view of `a` (no copy when it already is one)"""
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def model_pair_scores(J_ij, f_ij, f_i, device=0):
+    """FN of the zero-sum-gauged couplings and mutual information of every pair: the arithmetic of
+    `CouplingsModel._calculate_ecs` (couplings/model.py:777-799).  J_ij, f_ij: dense [L,L,q,q] (only the i<j blocks
+    are read), f_i: [L,q].  Returns (fn, mi), symmetric [L,L] float64 with a zero diagonal; mi is +inf for a pair with
+    f_ij(a,b) > 0 where f_i(a) f_j(b) = 0, as numpy gives."""
+    lib = _lib.load()
+    # float32 f_i (the plmc_v2 reader's): numpy's outer product f_i f_j^T is float32 then; the kernel rounds it the same way
+    flags = MODEL_FI_PRODUCT_F32 if np.asarray(f_i).dtype == np.float32 else 0
+    J_ij, f_ij, f_i = _f64(J_ij), _f64(f_ij), _f64(f_i)
+    L, q = f_i.shape
+    if J_ij.shape != (L, L, q, q) or f_ij.shape != (L, L, q, q):
+        raise ValueError("J_ij and f_ij must be (%d, %d, %d, %d)" % (L, L, q, q))
+    fn, mi = np.empty((L, L)), np.empty((L, L))
+    check(lib.plm_model_pair_scores_ex(_ptr(J_ij), _ptr(f_ij), _ptr(f_i), L, q, flags, device, None, _ptr(fn),
+                                       _ptr(mi)))
+    return fn, mi
+
+
+def double_mutant_matrix(J_ij, smm, target, device=0):
+    """`CouplingsModel.double_mut_mat` (couplings/model.py:715-742): dense [L,L,q,q] float64 with
+    D[i,j,a,b] = smm[i,a] + smm[j,b] + J_ij[a,b] - J_ij[a,t_j] - J_ij[t_i,b] + J_ij[t_i,t_j], D[j,i] = D[i,j].T and
+    zero diagonal blocks.  smm: [L,q] single-mutant matrix of the target, target: L states."""
+    lib = _lib.load()
+    J_ij, smm = _f64(J_ij), _f64(smm)
+    L, q = smm.shape
+    if J_ij.shape != (L, L, q, q):
+        raise ValueError("J_ij must be (%d, %d, %d, %d)" % (L, L, q, q))
+    target = np.ascontiguousarray(np.asarray(target).ravel(), dtype=np.int8)
+    if target.shape != (L,):
+        raise ValueError("target must hold %d states" % L)
+    D = np.empty((L, L, q, q))
+    check(lib.plm_double_mutants(_ptr(J_ij), _ptr(smm), _ptr(target), L, q, device, None, _ptr(D)))
+    return D
+
+
+def independent_fields(f_i, lambda_h, n_eff, device=0):
+    """Fields of the L2-regularised independent-site model, site by site
+    argmin_x n_eff (logZ(x) - f_i.x) + lambda_h |x|^2 (the objective of `CouplingsModel.to_independent_model`,
+    couplings/model.py:894-910), by damped Newton on the GPU.  Returns (h [L,q] float64, Newton steps [L] int32).
+    lambda_h must be > 0."""
+    lib = _lib.load()
+    f_i = _f64(f_i)
+    L, q = f_i.shape
+    h, iters = np.empty((L, q)), np.empty(L, np.int32)
+    check(lib.plm_independent_fields(_ptr(f_i), L, q, float(lambda_h), float(n_eff), device, None, _ptr(h),
+                                     _ptr(iters)))
+    return h, iters
+
+
 FLAG_IGNORE_GAPS = 2
 FLAG_SHARDED_STATE = 4
 FLAG_PRECOND = 8

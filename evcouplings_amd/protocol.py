@@ -14,7 +14,8 @@ The alternative that needs no Python hook at all is the CLI shim: ``tools: plmc:
 
 ``install_all()`` additionally installs the optional GPU drop-ins of the rows SURVEY.md section 8f lists:
 statistical energies behind ``CouplingsModel`` (``model_accel``), mean-field DCA (``mean_field``) and the
-alignment statistics behind ``Alignment`` (``alignment_accel``).
+alignment statistics behind ``Alignment`` (``alignment_accel``); ``install_all(analysis=True)`` adds the numeric
+analysis of ``CouplingsModel`` (EC scores, double mutants, independent model; off by default).
 """
 from evcouplings_amd import tools
 
@@ -96,11 +97,12 @@ def unregister_protocols():
         cp.PROTOCOLS.pop(name, None)
 
 
-def install_all():
-    """run_plmc + the N2 / N3 / N4 drop-ins (model energies, alignment statistics, mean-field DCA)."""
+def install_all(analysis=False):
+    """run_plmc + the N2 / N3 / N4 drop-ins (model energies, alignment statistics, mean-field DCA); with `analysis`
+    also CouplingsModel's EC scores, double-mutant matrix and independent model (model_accel.install(analysis=True))."""
     from evcouplings_amd import alignment_accel, mean_field, model_accel
     install()
-    model_accel.install()
+    model_accel.install(analysis=analysis)
     mean_field.install()
     alignment_accel.install()
 

@@ -254,6 +254,35 @@ int plm_hamiltonians(const int8_t *seqs, int32_t n, int32_t n_sites, int32_t n_s
 int plm_potentials(const int8_t *seqs, int32_t n, int32_t n_sites, int32_t n_states,
                    const float *x_canonical, int device, void *stream, float *potentials_out);
 
+/* ---- analysis of a fitted model: the numeric rest of CouplingsModel (DESIGN_NEXT_ROWS.md section 9.5) ---------
+ * float64 throughout, host buffers in and out.  Dense [L][L][q][q] inputs are read in their i<j blocks only (the row
+ * tails J[i, i+1:], L-1 copies into a compact device buffer).  PLM_EUNSUPPORTED for q outside 2..32; PLM_ENOMEM before
+ * any allocation when the device lacks the memory.
+ * plm_model_pair_scores replaces CouplingsModel._calculate_ecs's arithmetic (evcouplings/couplings/model.py:777-799):
+ *   the zero-sum gauge over all q states (_zero_sum_gauge, model.py:180-233), fn = its Frobenius norm, and
+ *   mi = sum_{f_ij(a,b) > 0} f_ij(a,b) log(f_ij(a,b) / (f_i(a) f_j(b))) -- +inf where f_ij > 0 meets f_i f_j = 0.
+ *   jij_full, fij_full: dense [L][L][q][q] doubles, only i<j blocks read; fi: [L][q]; fn_out, mi_out: [L][L],
+ *   symmetric, zero diagonal.                                                                                    */
+int plm_model_pair_scores(const double *jij_full, const double *fij_full, const double *fi, int32_t n_sites,
+                          int32_t n_states, int device, void *stream, double *fn_out, double *mi_out);
+/* the same with flags: PLM_MODEL_FI_PRODUCT_F32 rounds f_i(a) f_j(b) to float32 before the division -- what numpy's
+ * outer product gives for the float32 f_i a plmc_v2 .model file holds (model.py:797 np.dot of two float32 rows) */
+#define PLM_MODEL_FI_PRODUCT_F32 1
+int plm_model_pair_scores_ex(const double *jij_full, const double *fij_full, const double *fi, int32_t n_sites,
+                             int32_t n_states, int32_t flags, int device, void *stream, double *fn_out, double *mi_out);
+/* plm_double_mutants replaces CouplingsModel.double_mut_mat (model.py:715-742):
+ *   D[i][j][a][b] = smm[i][a] + smm[j][b] + J_ij(a,b) - J_ij(a,t_j) - J_ij(t_i,b) + J_ij(t_i,t_j), D[j][i] = D[i][j]^T,
+ *   zero diagonal blocks.  smm: [L][q] single-mutant dH of the target; target: L states 0..q-1;
+ *   dmm_out: dense [L][L][q][q].                                                                                 */
+int plm_double_mutants(const double *jij_full, const double *smm, const int8_t *target, int32_t n_sites,
+                       int32_t n_states, int device, void *stream, double *dmm_out);
+/* plm_independent_fields replaces the per-site fmin_bfgs of CouplingsModel.to_independent_model (model.py:882-927):
+ *   h_i = argmin_x n_eff (log sum_a exp x_a - f_i.x) + lambda_h |x|^2, by damped Newton to |g|_inf <= 1e-12 max(1, n_eff).
+ *   fi: [L][q]; h_out: [L][q]; iters_out: [L] Newton steps per site, may be NULL.  PLM_EINVAL for lambda_h <= 0 (the
+ *   optimum need not exist); PLM_ENUMERIC if a site does not converge within the step cap (h_out holds the last iterates). */
+int plm_independent_fields(const double *fi, int32_t n_sites, int32_t n_states, double lambda_h, double n_eff,
+                           int device, void *stream, double *h_out, int32_t *iters_out);
+
 /* ---- mean-field direct coupling analysis ---------------------------
  * Replaces the arithmetic of evcouplings/couplings/mean_field.py:163-222 (MeanFieldDCA.fit: weights,
  * frequencies, pseudo-count regularisation :717-790, covariance matrix :897-940, J = -C^-1 :204-210 and
