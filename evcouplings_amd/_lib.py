@@ -57,6 +57,14 @@ class PlmMfResult(C.Structure):
     ]
 
 
+class PlmSampleOpts(C.Structure):
+    _fields_ = [
+        ("n_chains", C.c_int32), ("burn_in", C.c_int32), ("n_snapshots", C.c_int32), ("thin", C.c_int32),
+        ("beta", C.c_float), ("seed", C.c_uint64),
+        ("start", C.c_void_p), ("fixed", C.c_void_p), ("allowed", C.c_void_p),
+    ]
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -86,6 +94,7 @@ SYMBOLS = [
     ("plm_model_pair_scores_ex", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int, _P, _P, _P]),
     ("plm_double_mutants", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),
     ("plm_independent_fields", C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P, _P, _P]),
+    ("plm_sample", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmSampleOpts), C.c_int, _P, _P, _P]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),

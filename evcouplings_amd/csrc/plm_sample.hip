@@ -1,0 +1,590 @@
+// plm_sample.hip -- Gibbs sampler of a fitted Potts model on gfx950: draw sequences from
+//     P(x) ~ exp beta (sum_i h_i(x_i) + sum_{i<j} J_ij(x_i, x_j)).
+// The reference has no sampler (its numba loops stop at _hamiltonians / _delta_hamiltonian, couplings/model.py:25-177);
+// the contract, the random-number scheme and the layout are in DESIGN_NEXT_ROWS.md section 9.6.
+//
+//   k_sample_expand  canonical i<j blocks -> W[i][j][b][a] = J_ij(a, b) for every ordered pair, float32, a contiguous and
+//                    padded to a multiple of 4 states, followed by the fields padded the same way
+//   k_gibbs          a workgroup owns a tile of chains (one lane per chain, the conditional's q energies in VGPRs) and
+//                    walks sweeps x sites itself; W rows reach the lanes through LDS in chunks of j
+//   k_gibbs_direct   the other form: lanes = (chain, state), W rows read straight from global memory
+//   k_field_energy   (H, H_J, H_h) of the field-only model (L = 1), which the forward GEMM of plm_hamiltonians cannot take
+#include "../../include/plm_hip.h"
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+
+int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
+int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
+
+namespace {
+
+#define GS_Q 32                 // largest alphabet
+#define GS_PF 8                 // float4 of a W chunk one thread carries from global memory to LDS
+#define GS_DEPTH 3              // chunks in flight per thread (the three register sets of k_gibbs)
+#define GS_LDS_BYTES 163840     // LDS of a CU
+#define GS_START_SWEEP 0xFFFFFFFFu
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11); only word 0 of the block is used
+__device__ __forceinline__ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                 uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+__device__ __forceinline__ int64_t pair_index(int i, int j, int L) {   // i < j, row-major
+    return (int64_t)i * (2 * L - i - 1) / 2 + (j - i - 1);
+}
+
+// W[((i L + j) q + b) QS + a] = J_ij(a, b); zero for i == j and for the padding states a >= q.  The fields follow at
+// W + L L q QS as [L][QS].  One thread per float4 of the output.
+__global__ __launch_bounds__(256) void k_sample_expand(const float *__restrict__ canon, int L, int q, int QS,
+                                                      float4 *__restrict__ W) {
+    const int NV = QS >> 2;
+    const int64_t n_w = (int64_t)L * L * q * NV, n_all = n_w + (int64_t)L * NV;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_all) return;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t >= n_w) {
+        const int64_t r = t - n_w;
+        const int i = (int)(r / NV), a0 = (int)(r % NV) * 4;
+        for (int k = 0; k < 4; k++)
+            if (a0 + k < q) v[k] = canon[(int64_t)i * q + a0 + k];
+    } else {
+        const int a0 = (int)(t % NV) * 4;
+        int64_t r = t / NV;
+        const int b = (int)(r % q);
+        r /= q;
+        const int j = (int)(r % L), i = (int)(r / L);
+        const float *J = canon + (int64_t)L * q;
+        if (i != j)
+            for (int k = 0; k < 4; k++) {
+                const int a = a0 + k;
+                if (a < q)
+                    v[k] = i < j ? J[(pair_index(i, j, L) * q + a) * q + b] : J[(pair_index(j, i, L) * q + b) * q + a];
+            }
+    }
+    W[t] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// One draw of the contract: e_a = exp(beta U_a - max) over the allowed states in state order, running sum S_a, the new
+// state is the first allowed a with S_a > u S_last (the last allowed state if none).  U holds NV float4 (states a >= q
+// are padding).  u = ((word0 >> 8) + 0.5) 2^-24.
+template <int NV>
+__device__ __forceinline__ int draw_state(const float4 *U, int q, uint32_t allowed, float beta, uint32_t word0) {
+    float e[NV * 4];
+    float m = -INFINITY;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        e[4 * v + 0] = __fmul_rn(beta, U[v].x);
+        e[4 * v + 1] = __fmul_rn(beta, U[v].y);
+        e[4 * v + 2] = __fmul_rn(beta, U[v].z);
+        e[4 * v + 3] = __fmul_rn(beta, U[v].w);
+    }
+#pragma unroll
+    for (int a = 0; a < NV * 4; a++)
+        if (a < q && ((allowed >> a) & 1u)) m = fmaxf(m, e[a]);
+    float S = 0.f;
+#pragma unroll
+    for (int a = 0; a < NV * 4; a++) {
+        const bool on = a < q && ((allowed >> a) & 1u);
+        S += on ? expf(__fsub_rn(e[a], m)) : 0.f;
+        e[a] = S;                                   // the running sum; flat across states that are not allowed
+    }
+    const float u = __fmul_rn((float)(word0 >> 8) + 0.5f, 5.9604644775390625e-08f);
+    const float t = __fmul_rn(u, S);
+    int pick = -1, last = 0;
+#pragma unroll
+    for (int a = 0; a < NV * 4; a++) {
+        const bool on = a < q && ((allowed >> a) & 1u);
+        if (on) last = a;
+        if (on && pick < 0 && e[a] > t) pick = a;
+    }
+    return pick < 0 ? last : pick;
+}
+
+// The two steps of the pipeline as macros over register sets with named members.  The members are native vectors: a
+// float4 (a struct) is assigned between address spaces by memcpy, which kept the sets in scratch memory, with a wait
+// after every load.
+typedef float gs_f4 __attribute__((ext_vector_type(4)));
+struct PreSet { gs_f4 a0, a1, a2, a3, a4, a5, a6, a7; };    // GS_PF float4
+#define GS_FOR_P(X, pr) X(0, pr) X(1, pr) X(2, pr) X(3, pr) X(4, pr) X(5, pr) X(6, pr) X(7, pr)
+#define GS_LOAD_P(p, pr) pr.a##p = ((const gs_f4 *)src4)[min(tid + p * TILE, n4 - 1)];   /* past the chunk: a copy that is not stored */
+#define GS_STORE_P(p, pr) { const int k = tid + p * TILE; if (k < n4) ((gs_f4 *)buf)[(k / NV) * NVP + (k % NV)] = pr.a##p; }
+#define GS_FETCH(ch_, pr) do { \
+                if ((ch_) < n_chunks) { \
+                    const int n4 = (min(L, ((ch_) + 1) * JC) - (ch_) * JC) * row4; \
+                    const float4 *src4 = Wi + (int64_t)(ch_) * JC * row4; \
+                    GS_FOR_P(GS_LOAD_P, pr) \
+                } \
+    } while (0)
+#define GS_STEP(ch_, pr) do { \
+                    if ((ch_) < n_chunks) { \
+                        const int j0 = (ch_) * JC, j1 = min(L, j0 + JC); \
+                        float4 *buf = stage + (g & 1u) * buf_f4; \
+                        g++; \
+                        const int n4 = (j1 - j0) * row4; \
+                        GS_FOR_P(GS_STORE_P, pr) \
+                        GS_FETCH((ch_) + GS_DEPTH, pr); \
+                        __syncthreads(); \
+                        int j = j0; \
+                        while (j < j1) { \
+                            const uint32_t word = xw[(j >> 2) * TILE + tid]; \
+                            if ((j & 3) == 0 && j + 4 <= j1) { \
+                                const float4 *r0 = buf + ((j - j0) * q + (word & 0xff)) * NVP; \
+                                const float4 *r1 = buf + ((j + 1 - j0) * q + ((word >> 8) & 0xff)) * NVP; \
+                                const float4 *r2 = buf + ((j + 2 - j0) * q + ((word >> 16) & 0xff)) * NVP; \
+                                const float4 *r3 = buf + ((j + 3 - j0) * q + (word >> 24)) * NVP; \
+                                float4 w0[NV], w1[NV], w2[NV], w3[NV]; \
+_Pragma("unroll") \
+                                for (int v = 0; v < NV; v++) { w0[v] = r0[v]; w1[v] = r1[v]; w2[v] = r2[v]; w3[v] = r3[v]; } \
+_Pragma("unroll") \
+                                for (int v = 0; v < NV; v++) { \
+                                    U[v].x += w0[v].x; U[v].y += w0[v].y; U[v].z += w0[v].z; U[v].w += w0[v].w; \
+                                    U[v].x += w1[v].x; U[v].y += w1[v].y; U[v].z += w1[v].z; U[v].w += w1[v].w; \
+                                    U[v].x += w2[v].x; U[v].y += w2[v].y; U[v].z += w2[v].z; U[v].w += w2[v].w; \
+                                    U[v].x += w3[v].x; U[v].y += w3[v].y; U[v].z += w3[v].z; U[v].w += w3[v].w; \
+                                } \
+                                j += 4; \
+                            } else { \
+                                if (j != i) { \
+                                    const int x = (word >> (8 * (j & 3))) & 0xff; \
+                                    const float4 *row = buf + ((j - j0) * q + x) * NVP; \
+_Pragma("unroll") \
+                                    for (int v = 0; v < NV; v++) { \
+                                        const float4 w = row[v]; \
+                                        U[v].x += w.x; U[v].y += w.y; U[v].z += w.z; U[v].w += w.w; \
+                                    } \
+                                } \
+                                j++; \
+                            } \
+                        } \
+                    } \
+    } while (0)
+
+// Chain states of the tile live in LDS as xs[L/4][TILE][4] bytes: a lane reads four consecutive sites of its chain with
+// one ds_read_b32, and the 64 lanes of a wave read 256 consecutive bytes.  A chunk of JC blocks W[i][j0 .. j0+JC) is
+// contiguous in global memory; the workgroup copies it into one of two LDS buffers (rows padded from NV to NVP float4
+// so that 16 lanes with 16 different rows hit 16 different 4-bank groups of a ds_read_b128) while it computes from the
+// other.  Sites are visited 0 .. L-1, and U accumulates in float32 over j = 0 .. L-1 without i: the order of the
+// contract.  src == NULL: the chains start from the start rule (one draw per site of softmax beta h_i).
+template <int NV, int TILE>
+__global__ __launch_bounds__(TILE) void k_gibbs(const float4 *__restrict__ W, int L, int q, int C, int JC,
+                                                const int8_t *__restrict__ src /* [C][L] or NULL: start rule */,
+                                                const uint8_t *__restrict__ fixed /* [L] or NULL */, uint32_t allowed,
+                                                float beta, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep0,
+                                                int n_sweeps, int8_t *__restrict__ dst /* [C][L] */) {
+    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;
+    extern __shared__ float4 lds4[];
+    const int tid = threadIdx.x;
+    const int L4 = (L + 3) >> 2;
+    const int c0 = blockIdx.x * TILE;
+    const int chain = c0 + tid;
+    const int n_here = min(TILE, C - c0);
+    const int buf_f4 = JC * q * NVP;                          // one staging buffer, in float4
+    float4 *stage = lds4;
+    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);
+    uint32_t *xw = (uint32_t *)xs;
+    const float4 *H = W + (int64_t)L * L * q * NV;
+
+    // ---- initial states ----
+    for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
+    __syncthreads();
+    if (src) {
+        for (int k = tid; k < n_here * L; k += TILE) {
+            const int c = k / L, j = k - c * L;
+            xs[((j >> 2) * TILE + c) * 4 + (j & 3)] = (uint8_t)src[(int64_t)c0 * L + k];
+        }
+    } else {
+        for (int i = 0; i < L; i++) {
+            float4 U[NV];
+#pragma unroll
+            for (int v = 0; v < NV; v++) U[v] = H[i * NV + v];
+            const int a = draw_state<NV>(U, q, allowed, beta, philox_word0((uint32_t)chain, 0u, GS_START_SWEEP,
+                                                                           (uint32_t)i, seed_lo, seed_hi));
+            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;
+        }
+    }
+    __syncthreads();
+
+    const int n_chunks = (L + JC - 1) / JC;
+    const int row4 = q * NV;                                  // float4 of one block W[i][j]
+    uint32_t g = 0;                                           // chunks staged so far: the LDS buffer alternates with it
+    for (int s = 0; s < n_sweeps; s++) {
+        const uint32_t sweep = sweep0 + (uint32_t)s;
+        for (int i = 0; i < L; i++) {
+            if (fixed && fixed[i]) continue;                  // uniform over the workgroup
+            const float4 *Wi = W + (int64_t)i * L * row4;
+            float4 U[NV];
+#pragma unroll
+            for (int v = 0; v < NV; v++) U[v] = H[i * NV + v];
+            // GS_DEPTH chunks are in flight in registers (one LDS round trip per chunk would leave the sweep bound by
+            // the latency of the loads: measured, section 9.6)
+            PreSet pre0, pre1, pre2;
+            GS_FETCH(0, pre0);
+            GS_FETCH(1, pre1);
+            GS_FETCH(2, pre2);
+            for (int base = 0; base < n_chunks; base += GS_DEPTH) {
+                GS_STEP(base, pre0);
+                GS_STEP(base + 1, pre1);
+                GS_STEP(base + 2, pre2);
+            }
+            const int a = draw_state<NV>(U, q, allowed, beta,
+                                         philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
+            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;   // a lane reads only its own chain: no barrier
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < n_here * L; k += TILE) {
+        const int c = k / L, j = k - c * L;
+        dst[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
+    }
+}
+
+// The same draw with one lane per state (groups of QP lanes, QP a power of two >= q): the maximum by a butterfly, the
+// running sum by every lane of the group in state order -- the same additions in the same order as draw_state, so the
+// two forms of the sweep give the same states bit for bit.
+template <int QP>
+__device__ __forceinline__ int draw_group(float U, int a, int q, uint32_t allowed, float beta, uint32_t word0) {
+    const bool on = a < q && ((allowed >> a) & 1u);
+    const float bu = __fmul_rn(beta, U);
+    float m = on ? bu : -INFINITY;
+#pragma unroll
+    for (int o = QP / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    const float e = on ? expf(__fsub_rn(bu, m)) : 0.f;
+    const int base = (threadIdx.x & 63) & ~(QP - 1);
+    float S = 0.f;
+    for (int b = 0; b < q; b++) S += __shfl(e, base + b, 64);
+    const float u = __fmul_rn((float)(word0 >> 8) + 0.5f, 5.9604644775390625e-08f);
+    const float t = __fmul_rn(u, S);
+    int pick = -1, last = 0;
+    S = 0.f;
+    for (int b = 0; b < q; b++) {
+        S += __shfl(e, base + b, 64);
+        const bool okb = (allowed >> b) & 1u;
+        if (okb) last = b;
+        if (okb && pick < 0 && S > t) pick = b;
+    }
+    return pick < 0 ? last : pick;
+}
+
+// The other form of the sweep: lanes = (chain, state), 256 / QP chains per workgroup, the row W[i][j][x_cj][.] read
+// straight from global memory (every workgroup walks the same rows at about the same time, so they come from L2).  No
+// staging and little LDS (the chain states, [chain][L] bytes), but 64 / QP chains per wave instead of 64.  It serves
+// the lengths whose chain states do not fit the LDS in the tiled form, and PLM_SAMPLE_FORM=direct selects it for
+// measurements (tests/probes/sample_probe.py).
+template <int QP>
+__global__ __launch_bounds__(256) void k_gibbs_direct(const float *__restrict__ Wf, int L, int q, int QS, int C,
+                                                      const int8_t *__restrict__ src, const uint8_t *__restrict__ fixed,
+                                                      uint32_t allowed, float beta, uint32_t seed_lo, uint32_t seed_hi,
+                                                      uint32_t sweep0, int n_sweeps, int8_t *__restrict__ dst) {
+    constexpr int CPW = 256 / QP;
+    extern __shared__ float4 lds4[];
+    uint8_t *xs = (uint8_t *)lds4;
+    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;
+    const int Lp = (L + 3) & ~3;
+    const int c0 = blockIdx.x * CPW;
+    const int chain = c0 + cl;
+    const int n_here = min(CPW, C - c0);
+    const float *Hf = Wf + (int64_t)L * L * q * QS;
+    for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
+    __syncthreads();
+    if (src) {
+        for (int k = tid; k < n_here * L; k += 256) {
+            const int c = k / L, j = k - c * L;
+            xs[c * Lp + j] = (uint8_t)src[(int64_t)c0 * L + k];
+        }
+    } else {
+        for (int i = 0; i < L; i++) {
+            const float U = a < q ? Hf[i * QS + a] : 0.f;
+            const int x = draw_group<QP>(U, a, q, allowed, beta,
+                                         philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i, seed_lo, seed_hi));
+            if (a == 0) xs[cl * Lp + i] = (uint8_t)x;
+        }
+    }
+    __syncthreads();
+    for (int s = 0; s < n_sweeps; s++) {
+        const uint32_t sweep = sweep0 + (uint32_t)s;
+        for (int i = 0; i < L; i++) {
+            if (fixed && fixed[i]) continue;
+            const float *Wi = Wf + (int64_t)i * L * q * QS;
+            float U = a < q ? Hf[i * QS + a] : 0.f;
+            const uint8_t *xc = xs + cl * Lp;
+            for (int j = 0; j < L; j++) {
+                if (j == i) continue;
+                const int x = xc[j];
+                if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
+            }
+            const int x = draw_group<QP>(U, a, q, allowed, beta,
+                                         philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
+            if (a == 0) xs[cl * Lp + i] = (uint8_t)x;
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < n_here * L; k += 256) {
+        const int c = k / L, j = k - c * L;
+        dst[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
+    }
+}
+
+// (H, H_J, H_h) = (h(x), 0, h(x)) of the one-site model
+__global__ void k_field_energy(const float *__restrict__ h, const int8_t *__restrict__ x, int64_t n, double *__restrict__ en) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const double v = (double)h[x[t]];
+    en[3 * t + 0] = v;
+    en[3 * t + 1] = 0.0;
+    en[3 * t + 2] = v;
+}
+
+struct Plan {
+    int NV, NVP, tile, JC;
+    size_t lds;
+};
+
+// tile of chains per workgroup, j-chunk and LDS size: the largest tile that still gives every CU a workgroup, limited
+// by what the chain states leave of the LDS
+bool make_plan(int L, int q, int C, int n_cu, Plan *out) {
+    Plan p;
+    p.NV = (q + 3) / 4;
+    p.NVP = (p.NV % 2 == 0) ? p.NV + 1 : p.NV;
+    const int L4 = (L + 3) / 4;
+    const int tiles[3] = {256, 128, 64};
+    const int cands[6] = {16, 12, 8, 4, 2, 1};
+    for (int t = 0; t < 3; t++) {
+        p.tile = tiles[t];
+        if (t < 2 && (C + p.tile - 1) / p.tile < n_cu) continue;          // spread small calls over the CUs
+        const size_t xs = (size_t)L4 * p.tile * 4;
+        for (int c = 0; c < 6 && (p.JC = cands[c]); c++) {
+            if (p.JC > 1 && p.JC >= 2 * L) continue;
+            if ((size_t)p.JC * q * p.NV > (size_t)GS_PF * p.tile) continue;  // a chunk is GS_PF float4 per thread
+            p.lds = 2 * (size_t)p.JC * q * p.NVP * 16 + xs;
+            if (p.lds <= GS_LDS_BYTES) {
+                *out = p;
+                return true;
+            }
+        }
+    }
+    // the smaller tiles, whatever the CU count
+    for (int t = 1; t < 3; t++) {
+        p.tile = tiles[t];
+        const size_t xs = (size_t)L4 * p.tile * 4;
+        for (int c = 0; c < 6 && (p.JC = cands[c]); c++) {
+            if ((size_t)p.JC * q * p.NV > (size_t)GS_PF * p.tile) continue;
+            p.lds = 2 * (size_t)p.JC * q * p.NVP * 16 + xs;
+            if (p.lds <= GS_LDS_BYTES) {
+                *out = p;
+                return true;
+            }
+        }
+    }
+    return false;
+}
+
+template <int NV, int TILE>
+hipError_t launch_gibbs_t(const Plan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
+                          const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
+                          int8_t *dst) {
+    auto kern = k_gibbs<NV, TILE>;
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((C + TILE - 1) / TILE)), dim3(TILE), p.lds, st, W, L, q, C, p.JC, src, fixed,
+                       allowed, beta, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), sweep0, n_sweeps, dst);
+    return hipGetLastError();
+}
+
+template <int NV>
+hipError_t launch_gibbs_nv(const Plan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
+                           const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
+                           int8_t *dst) {
+    switch (p.tile) {
+    case 256: return launch_gibbs_t<NV, 256>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    case 128: return launch_gibbs_t<NV, 128>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    default: return launch_gibbs_t<NV, 64>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    }
+}
+
+hipError_t launch_gibbs(const Plan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
+                        const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
+                        int8_t *dst) {
+#define GS_CASE(n) \
+    case n: return launch_gibbs_nv<n>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    switch (p.NV) {
+        GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE(8)
+    }
+#undef GS_CASE
+    return hipErrorInvalidValue;
+}
+
+template <int QP>
+hipError_t launch_direct_t(hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src, const uint8_t *fixed,
+                           uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps, int8_t *dst) {
+    constexpr int CPW = 256 / QP;
+    const size_t lds = (size_t)CPW * ((L + 3) / 4 * 4);
+    auto kern = k_gibbs_direct<QP>;
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((C + CPW - 1) / CPW)), dim3(256), lds, st, (const float *)W, L, q,
+                       (q + 3) / 4 * 4, C, src, fixed, allowed, beta, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
+                       sweep0, n_sweeps, dst);
+    return hipGetLastError();
+}
+
+int direct_group(int q) { return q <= 2 ? 2 : q <= 4 ? 4 : q <= 8 ? 8 : q <= 16 ? 16 : 32; }
+bool direct_fits(int L, int q) { return (size_t)(256 / direct_group(q)) * ((L + 3) / 4 * 4) <= GS_LDS_BYTES; }
+
+hipError_t launch_direct(hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src, const uint8_t *fixed,
+                         uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps, int8_t *dst) {
+    switch (direct_group(q)) {
+    case 2: return launch_direct_t<2>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    case 4: return launch_direct_t<4>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    case 8: return launch_direct_t<8>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    case 16: return launch_direct_t<16>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    default: return launch_direct_t<32>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    }
+}
+
+}  // namespace
+
+int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_sample_opts *opts, int device,
+               void *stream, int8_t *samples_out, double *energies_out) {
+    if (!opts) return plm_fail(PLM_EINVAL, "NULL options");
+    const int L = n_sites, q = n_states, C = opts->n_chains, K = opts->n_snapshots;
+    if (L < 1 || C < 1 || K < 1 || opts->burn_in < 0 || (K > 1 && opts->thin < 1))
+        return plm_fail(PLM_EINVAL, "need n_sites >= 1, n_chains >= 1, n_snapshots >= 1, burn_in >= 0, thin >= 1 "
+                                    "(got %d, %d, %d, %d, %d)", L, C, K, opts->burn_in, opts->thin);
+    if (q < 2 || q > GS_Q) return plm_fail(PLM_EUNSUPPORTED, "the sampler supports 2..32 states (got %d)", q);
+    if (!(opts->beta > 0.f) || !isfinite(opts->beta))
+        return plm_fail(PLM_EINVAL, "beta must be finite and > 0 (got %g)", (double)opts->beta);
+    const int thin = K > 1 ? opts->thin : 0;
+    if ((double)opts->burn_in + (double)(K - 1) * thin >= 4294967295.0)
+        return plm_fail(PLM_EINVAL, "burn_in + (n_snapshots - 1) thin must stay below 2^32 - 1 sweeps");
+    int rc = plm_check_device(device);
+    if (rc) return rc;
+    // sizes first: nothing below this point is dereferenced before the device is known to hold the call
+    const int QS = (q + 3) / 4 * 4;
+    const double table_b = 4.0 * ((double)L * L * q * QS + (double)L * QS);
+    const double canon_b = 4.0 * ((double)L * q + (double)L * (L - 1) / 2 * q * q);
+    const double state_b = (double)C * L * ((double)K + 1.0) + L;
+    const double energy_b = energies_out ? 24.0 * C : 0.0;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipMemGetInfo failed");
+    if (table_b + canon_b + state_b + energy_b > (double)free_b)
+        return plm_fail(PLM_ENOMEM, "the sampler needs %.2f GB of device memory (%.2f GB of it the expanded couplings), "
+                                    "%.2f GB are free (of %.1f GB)", (table_b + canon_b + state_b + energy_b) / 1e9,
+                        table_b / 1e9, free_b / 1e9, total_b / 1e9);
+    if ((double)C * L * K >= 9.0e18 || (double)C * L >= 2147483647.0)
+        return plm_fail(PLM_EINVAL, "n_chains x n_sites must stay below 2^31");
+    if (!x_canonical || !samples_out) return plm_fail(PLM_EINVAL, "NULL argument");
+    uint32_t allowed = q == 32 ? 0xFFFFFFFFu : ((1u << q) - 1u);
+    if (opts->allowed) {
+        uint32_t m = 0;
+        for (int a = 0; a < q; a++)
+            if (opts->allowed[a]) m |= 1u << a;
+        if (!m) return plm_fail(PLM_EINVAL, "no state is allowed");
+        allowed = m;
+    }
+    if (opts->start)
+        for (size_t k = 0; k < (size_t)C * L; k++) {
+            const int v = opts->start[k];
+            const int site = (int)(k % (size_t)L);
+            if (v < 0 || v >= q) return plm_fail(PLM_EINVAL, "start[%zu] = %d outside 0..%d", k, v, q - 1);
+            if (!((allowed >> v) & 1u) && !(opts->fixed && opts->fixed[site]))
+                return plm_fail(PLM_EINVAL, "start[%zu] = %d is not an allowed state and site %d is not fixed", k, v, site);
+        }
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDeviceProperties failed");
+    Plan plan;
+    // the tiled form wherever the chain states fit the LDS; the direct form for longer models, or on request
+    // (PLM_SAMPLE_FORM=direct | tiled, measurements only: the two forms return the same states)
+    const char *form = getenv("PLM_SAMPLE_FORM");
+    bool direct = form && !strcmp(form, "direct");
+    const bool tiled_fits = make_plan(L, q, C, prop.multiProcessorCount, &plan);
+    if (!tiled_fits && !(form && !strcmp(form, "tiled"))) direct = true;
+    if (direct ? !direct_fits(L, q) : !tiled_fits)
+        return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n_canon = (size_t)L * q + (size_t)L * (L - 1) / 2 * q * q;
+    const size_t n_w4 = ((size_t)L * L * q + (size_t)L) * (QS / 4);
+    const size_t CL = (size_t)C * L;
+    float *canon = nullptr;
+    float4 *W = nullptr;
+    int8_t *start = nullptr, *snaps = nullptr;
+    uint8_t *fixed = nullptr;
+    double *en = nullptr;
+    auto done = [&](int code) {
+        void *all[] = {canon, W, start, snaps, fixed, en};
+        for (void *b : all)
+            if (b) (void)hipFree(b);
+        return code;
+    };
+#define GS_ALLOC(ptr, bytes)                                                                   \
+    if (hipMalloc((void **)&ptr, std::max<size_t>((bytes), 16)) != hipSuccess) {               \
+        ptr = nullptr;                                                                         \
+        return done(plm_fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed", (size_t)(bytes)));   \
+    }
+    GS_ALLOC(canon, n_canon * sizeof(float));
+    GS_ALLOC(W, n_w4 * sizeof(float4));
+    GS_ALLOC(snaps, CL * (size_t)K);
+    if (opts->start) GS_ALLOC(start, CL);
+    if (opts->fixed) GS_ALLOC(fixed, (size_t)L);
+    if (energies_out && L == 1) GS_ALLOC(en, CL * (size_t)K * 3 * sizeof(double));
+#undef GS_ALLOC
+    hipError_t e;
+#define ET(expr)              \
+    if ((e = (expr)) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));
+    ET(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    if (start) ET(hipMemcpyAsync(start, opts->start, CL, hipMemcpyHostToDevice, st));
+    if (fixed) ET(hipMemcpyAsync(fixed, opts->fixed, (size_t)L, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sample_expand, dim3((unsigned)((n_w4 + 255) / 256)), dim3(256), 0, st, canon, L, q, QS, W);
+    ET(hipGetLastError());
+    for (int k = 0; k < K; k++) {
+        const int8_t *src = k == 0 ? start : snaps + (size_t)(k - 1) * CL;
+        const uint32_t sweep0 = k == 0 ? 0u : (uint32_t)opts->burn_in + (uint32_t)(k - 1) * (uint32_t)thin;
+        const int n_sweeps = k == 0 ? opts->burn_in : thin;
+        if (direct) {
+            ET(launch_direct(st, W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0, n_sweeps,
+                             snaps + (size_t)k * CL));
+        } else {
+            ET(launch_gibbs(plan, st, W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0, n_sweeps,
+                            snaps + (size_t)k * CL));
+        }
+    }
+    ET(hipMemcpyAsync(samples_out, snaps, CL * (size_t)K, hipMemcpyDeviceToHost, st));
+    if (energies_out && L == 1) {
+        const int64_t n = (int64_t)CL * K;
+        hipLaunchKernelGGL(k_field_energy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, canon, snaps, n, en);
+        ET(hipGetLastError());
+        ET(hipMemcpyAsync(energies_out, en, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    ET(hipStreamSynchronize(st));
+#undef ET
+    rc = done(PLM_OK);
+    if (energies_out && L > 1) {
+        // the statistical energies of the snapshots at beta = 1: the code path of plm_hamiltonians, in row chunks that
+        // stay inside its limit on sequences per call
+        const size_t Lp = ((size_t)L + 31) / 32 * 32;
+        const size_t max_rows = std::max<size_t>(256, (((size_t)1 << 30) / Lp) / 256 * 256);
+        const size_t rows = CL / (size_t)L * (size_t)K;
+        for (size_t r0 = 0; r0 < rows && rc == PLM_OK; r0 += max_rows) {
+            const size_t n = std::min(max_rows, rows - r0);
+            rc = plm_hamiltonians(samples_out + r0 * L, (int32_t)n, L, q, x_canonical, device, stream,
+                                  energies_out + r0 * 3);
+        }
+    }
+    return rc;
+}

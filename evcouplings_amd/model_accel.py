@@ -12,6 +12,8 @@ for a block-wise one -- host-side format code, same attributes; measured to be n
 `install(analysis=True)` also rebinds the numeric rest of the class (DESIGN_NEXT_ROWS.md section 9.5):
 `_calculate_ecs` (FN / MI / CN / the EC table), the `double_mut_mat` property and `to_independent_model`, on
 `plm_model_pair_scores`, `plm_double_mutants` and `plm_independent_fields`.  Off by default.
+`sample_sequences(model, n)` draws sequences from a model with the library's Gibbs sampler (`plm_sample`,
+DESIGN_NEXT_ROWS.md section 9.6); the reference has no sampler, so `install()` has nothing to rebind for it.
 """
 from copy import deepcopy
 
@@ -42,6 +44,74 @@ def single_mutant_hamiltonians(target_seq, J_ij, h_i):
     from evcouplings_amd import plm
     L, q = h_i.shape
     return plm.single_mutant_matrix(np.asarray(target_seq).astype(np.int8), q, h_i, _pairs_from_dense(J_ij))
+
+
+def sample_sequences(model, n_chains, burn_in=100, n_snapshots=1, thin=1, beta=1.0, seed=0, start=None, fixed=None,
+                     exclude="", as_letters=True, energies=False, device=0):
+    """
+    Draw sequences from P(x) ~ exp beta H(x) of a `CouplingsModel` (anything with `J_ij` [L, L, q, q], `h_i` [L, q],
+    `alphabet`, `target_seq` and `index_list`) with the Gibbs sampler of libplm_hip: n_chains independent chains, burn_in
+    sweeps, then n_snapshots snapshots thin sweeps apart.
+      start    None (one draw per site of softmax beta h_i), "target" (every chain starts from the target sequence), or an
+               (n_chains, L) matrix of letters or of states
+      fixed    positions in the model's own numbering (`index_list`) that keep the target's residue
+      exclude  letters that are never drawn, e.g. "-" for sequences without gaps
+    Returns an (n_snapshots * n_chains, L) matrix of letters (as_letters) or of int8 states, snapshots one after the
+    other; with energies=True a tuple of that and the (n_snapshots * n_chains, 3) energies (H, H_J, H_h) at beta = 1.
+    """
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    letters = np.array(list(model.alphabet) if isinstance(model.alphabet, str) else model.alphabet).astype("U1")
+    if len(letters) != q:
+        raise ValueError("the model's alphabet has %d letters, its fields %d states" % (len(letters), q))
+    code = {a: k for k, a in enumerate(letters)}
+
+    def states(mat):
+        mat = np.asarray(mat)
+        if mat.dtype.kind in "iu":
+            return mat.astype(np.int8)
+        try:
+            return np.vectorize(code.__getitem__, otypes=[np.int8])(mat.astype("U1"))
+        except KeyError as e:
+            raise ValueError("letter %s is not in the model's alphabet" % e)
+
+    target = states(np.array(list(model.target_seq)))
+    allowed = None
+    if exclude:
+        unknown = [a for a in exclude if a not in code]
+        if unknown:
+            raise ValueError("excluded letters %r are not in the model's alphabet" % "".join(unknown))
+        allowed = np.ones(q, np.uint8)
+        allowed[[code[a] for a in exclude]] = 0
+    flags = None
+    if fixed is not None and len(fixed):
+        pos = {int(p): k for k, p in enumerate(np.asarray(model.index_list))}
+        missing = [p for p in fixed if int(p) not in pos]
+        if missing:
+            raise ValueError("positions %r are not in the model's index_list" % missing)
+        flags = np.zeros(L, np.uint8)
+        flags[[pos[int(p)] for p in fixed]] = 1
+    if isinstance(start, str):
+        if start != "target":
+            raise ValueError('start must be None, "target" or a matrix')
+        x0 = np.tile(target, (int(n_chains), 1))
+    elif start is not None:
+        x0 = states(start).reshape(int(n_chains), L).copy()
+    elif flags is not None:
+        # the start rule knows no fixed sites: draw it, then put the target's residues there
+        x0 = plm.sample(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_chains, burn_in=0, beta=beta, seed=seed,
+                        allowed=allowed, energies=False, device=device)[0][0]
+    else:
+        x0 = None
+    if flags is not None:
+        x0[:, flags.astype(bool)] = target[flags.astype(bool)]
+    out, en = plm.sample(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_chains, burn_in=burn_in,
+                         n_snapshots=n_snapshots, thin=thin, beta=beta, seed=seed, start=x0, fixed=flags, allowed=allowed,
+                         energies=energies, device=device)
+    out = out.reshape(-1, L)
+    res = letters[out] if as_letters else out
+    return (res, en.reshape(-1, 3)) if energies else res
 
 
 def read_plmc_v2(self, f, precision):

@@ -158,6 +158,50 @@ def potentials(seqs, q, hi, jij, device=0):
     return out
 
 
+def sample(hi, jij, q, n_chains, burn_in=10, n_snapshots=1, thin=1, beta=1.0, seed=0, start=None, fixed=None,
+           allowed=None, energies=True, device=0):
+    """
+    Draw sequences from P(x) ~ exp beta (sum_i h_i(x_i) + sum_{i<j} J_ij(x_i, x_j)) with the Gibbs sampler of the library
+    (plm_sample, DESIGN_NEXT_ROWS.md section 9.6): n_chains independent chains, burn_in full sweeps (sites 0 .. L-1 in
+    order), then n_snapshots snapshots of all chains, thin sweeps apart.
+    hi: L x q; jij: the i<j blocks [L(L-1)/2][q][q] as for `hamiltonians`.  start: None (every chain starts from one draw
+    per site of softmax beta h_i) or n_chains x L states; fixed: None or L flags of sites that are never resampled;
+    allowed: None or q flags of the states that may be drawn.  The result depends on (seed, chain index, model, options)
+    only, not on n_chains or the run.
+    Returns (samples int8 [K, C, L], energies float64 [K, C, 3] = (H, H_J, H_h) at beta = 1, or None).
+    """
+    q, C_, K = int(q), int(n_chains), int(n_snapshots)
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
+        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
+    L = hi.shape[0]
+    jij = np.ascontiguousarray(jij, dtype=np.float32)
+    if jij.size != L * (L - 1) // 2 * q * q:
+        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    if C_ < 1 or K < 1 or int(burn_in) < 0 or int(thin) < 1:
+        raise ValueError("need n_chains >= 1, n_snapshots >= 1, burn_in >= 0 and thin >= 1")
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.int8)
+        if start.shape != (C_, L):
+            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8)
+        if fixed.shape != (L,):
+            raise ValueError("fixed must hold L = %d flags" % L)
+    if allowed is not None:
+        allowed = np.ascontiguousarray(np.asarray(allowed).astype(bool), dtype=np.uint8)
+        if allowed.shape != (q,):
+            raise ValueError("allowed must hold q = %d flags" % q)
+    lib = _lib.load()
+    opts = _lib.PlmSampleOpts(C_, int(burn_in), K, int(thin), float(beta), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                              _ptr(start), _ptr(fixed), _ptr(allowed))
+    samples = np.zeros((K, C_, L), dtype=np.int8)
+    en = np.zeros((K, C_, 3)) if energies else None
+    x = np.concatenate([hi.reshape(L * q), jij.reshape(-1)])
+    check(lib.plm_sample(L, q, _ptr(x), C.byref(opts), int(device), None, _ptr(samples), _ptr(en)))
+    return samples, en
+
+
 def single_mutant_matrix(target, q, hi, jij, device=0):
     """
     Energy differences of every single substitution of `target`: L x q x 3 float64 (dH, dH_J, dH_h), the

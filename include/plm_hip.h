@@ -283,6 +283,36 @@ int plm_double_mutants(const double *jij_full, const double *smm, const int8_t *
 int plm_independent_fields(const double *fi, int32_t n_sites, int32_t n_states, double lambda_h, double n_eff,
                            int device, void *stream, double *h_out, int32_t *iters_out);
 
+/* ---- sampling from a fitted model: Gibbs sampler (DESIGN_NEXT_ROWS.md section 9.6) --------------------------------
+ * Draws sequences from P(x) ~ exp beta (sum_i h_i(x_i) + sum_{i<j} J_ij(x_i, x_j)); nothing in the reference does this
+ * (its loops stop at _hamiltonians / _delta_hamiltonian, couplings/model.py:25-177).  C independent chains; one sweep
+ * visits the sites 0 .. L-1 in that order and draws x_ci ~ softmax_a beta (h_i(a) + sum_{j != i} J_ij(a, x_cj)) over the
+ * allowed states; fixed sites are skipped.  Random numbers: Philox4x32-10, counter (chain, 0, sweep, site), key (seed low,
+ * seed high); sweep counts from 0 across burn-in, thinning and snapshots; u = ((word0 >> 8) + 0.5) 2^-24; with
+ * e_a = exp(beta U_a - max) over the allowed states in state order and running sum S_a the new state is the first allowed
+ * a with S_a > u S_last.  start == NULL: chain c starts from one such draw per site of softmax beta h_i with sweep index
+ * 0xFFFFFFFF.  U accumulates in float32 over j = 0 .. L-1.  The result depends on (seed, chain index, model, options)
+ * only: not on n_chains, the device or the run.
+ * x_canonical: as plm_hamiltonians (q in 2..32, else PLM_EUNSUPPORTED; any n_sites >= 1 whose chain states fit the LDS,
+ * about 2 400).  samples_out: K x C x L states; energies_out: K x C x 3 doubles (H, H_J, H_h) of the snapshots at beta = 1,
+ * what plm_hamiltonians returns for those rows, or NULL.  PLM_ENOMEM before any allocation, and before any array is
+ * read, when the device cannot hold the expanded couplings (L^2 q ceil4(q) floats), the chain states and the outputs.
+ * PLM_EINVAL: start states outside 0..q-1, or not allowed at a site that is not fixed; no allowed state; beta not
+ * finite or <= 0. */
+typedef struct {
+    int32_t  n_chains;      /* C >= 1, independent chains                                            */
+    int32_t  burn_in;       /* full sweeps before the first snapshot, >= 0                           */
+    int32_t  n_snapshots;   /* K >= 1 snapshots of all chains                                        */
+    int32_t  thin;          /* sweeps between snapshots, >= 1 (ignored when K == 1)                  */
+    float    beta;          /* inverse temperature, > 0, finite                                      */
+    uint64_t seed;
+    const int8_t  *start;   /* NULL, or C x L states: initial state of every chain                   */
+    const uint8_t *fixed;   /* NULL, or L flags: sites that are never resampled                      */
+    const uint8_t *allowed; /* NULL, or q flags: states that may be drawn (at least one set)         */
+} plm_sample_opts;
+int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_sample_opts *opts,
+               int device, void *stream, int8_t *samples_out /* K x C x L */, double *energies_out /* K x C x 3 or NULL */);
+
 /* ---- mean-field direct coupling analysis ---------------------------
  * Replaces the arithmetic of evcouplings/couplings/mean_field.py:163-222 (MeanFieldDCA.fit: weights,
  * frequencies, pseudo-count regularisation :717-790, covariance matrix :897-940, J = -C^-1 :204-210 and
