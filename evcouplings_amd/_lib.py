@@ -65,6 +65,23 @@ class PlmSampleOpts(C.Structure):
     ]
 
 
+class PlmBmOpts(C.Structure):
+    _fields_ = [
+        ("n_chains", C.c_int32), ("n_epochs", C.c_int32), ("sweeps_per_epoch", C.c_int32), ("first_epoch", C.c_int32),
+        ("lr", C.c_float), ("lr_decay_after", C.c_int32), ("lambda_h", C.c_float), ("lambda_j", C.c_float),
+        ("tol", C.c_float), ("seed", C.c_uint64), ("start", C.c_void_p),
+    ]
+
+
+class PlmBmResult(C.Structure):
+    _fields_ = [
+        ("x_out", C.c_void_p), ("pi_out", C.c_void_p), ("pij_out", C.c_void_p), ("chains_out", C.c_void_p),
+        ("trace", C.c_void_p), ("epochs_done", C.c_int32), ("status", C.c_int32),
+    ]
+
+
+BM_EPOCH_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -95,6 +112,8 @@ SYMBOLS = [
     ("plm_double_mutants", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),
     ("plm_independent_fields", C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P, _P, _P]),
     ("plm_sample", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmSampleOpts), C.c_int, _P, _P, _P]),
+    ("plm_bm_fit", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(PlmBmOpts), C.c_int, _P, BM_EPOCH_CB, _P,
+                             C.POINTER(PlmBmResult)]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),

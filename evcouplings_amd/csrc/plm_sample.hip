@@ -10,6 +10,7 @@
 //   k_gibbs_direct   the other form: lanes = (chain, state), W rows read straight from global memory
 //   k_field_energy   (H, H_J, H_h) of the field-only model (L = 1), which the forward GEMM of plm_hamiltonians cannot take
 #include "../../include/plm_hip.h"
+#include "plm_sample_internal.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -351,15 +352,12 @@ __global__ void k_field_energy(const float *__restrict__ h, const int8_t *__rest
     en[3 * t + 2] = v;
 }
 
-struct Plan {
-    int NV, NVP, tile, JC;
-    size_t lds;
-};
+typedef gibbs::SweepPlan Plan;
 
 // tile of chains per workgroup, j-chunk and LDS size: the largest tile that still gives every CU a workgroup, limited
 // by what the chain states leave of the LDS
 bool make_plan(int L, int q, int C, int n_cu, Plan *out) {
-    Plan p;
+    Plan p = {};
     p.NV = (q + 3) / 4;
     p.NVP = (p.NV % 2 == 0) ? p.NV + 1 : p.NV;
     const int L4 = (L + 3) / 4;
@@ -460,6 +458,43 @@ hipError_t launch_direct(hipStream_t st, const float4 *W, int L, int q, int C, c
 
 }  // namespace
 
+namespace gibbs {
+
+int plan_sweeps(int L, int q, int C, int device, SweepPlan *out) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDeviceProperties failed");
+    Plan plan = {};
+    // the tiled form wherever the chain states fit the LDS; the direct form for longer models, or on request
+    // (PLM_SAMPLE_FORM=direct | tiled, measurements only: the two forms return the same states)
+    const char *form = getenv("PLM_SAMPLE_FORM");
+    bool direct = form && !strcmp(form, "direct");
+    const bool tiled_fits = make_plan(L, q, C, prop.multiProcessorCount, &plan);
+    if (!tiled_fits && !(form && !strcmp(form, "tiled"))) direct = true;
+    if (direct ? !direct_fits(L, q) : !tiled_fits)
+        return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
+    plan.direct = direct;
+    *out = plan;
+    return PLM_OK;
+}
+
+size_t table_float4(int L, int q) { return ((size_t)L * L * q + (size_t)L) * ((q + 3) / 4); }
+
+hipError_t expand(hipStream_t st, const float *canon, int L, int q, float4 *W) {
+    const size_t n_w4 = table_float4(L, q);
+    hipLaunchKernelGGL(k_sample_expand, dim3((unsigned)((n_w4 + 255) / 256)), dim3(256), 0, st, canon, L, q,
+                       (q + 3) / 4 * 4, W);
+    return hipGetLastError();
+}
+
+hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
+                  const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
+                  int8_t *dst) {
+    if (p.direct) return launch_direct(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    return launch_gibbs(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+}
+
+}  // namespace gibbs
+
 int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_sample_opts *opts, int device,
                void *stream, int8_t *samples_out, double *energies_out) {
     if (!opts) return plm_fail(PLM_EINVAL, "NULL options");
@@ -506,17 +541,10 @@ int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
             if (!((allowed >> v) & 1u) && !(opts->fixed && opts->fixed[site]))
                 return plm_fail(PLM_EINVAL, "start[%zu] = %d is not an allowed state and site %d is not fixed", k, v, site);
         }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDeviceProperties failed");
     Plan plan;
-    // the tiled form wherever the chain states fit the LDS; the direct form for longer models, or on request
-    // (PLM_SAMPLE_FORM=direct | tiled, measurements only: the two forms return the same states)
-    const char *form = getenv("PLM_SAMPLE_FORM");
-    bool direct = form && !strcmp(form, "direct");
-    const bool tiled_fits = make_plan(L, q, C, prop.multiProcessorCount, &plan);
-    if (!tiled_fits && !(form && !strcmp(form, "tiled"))) direct = true;
-    if (direct ? !direct_fits(L, q) : !tiled_fits)
-        return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
+    rc = gibbs::plan_sweeps(L, q, C, device, &plan);
+    if (rc) return rc;
+    const bool direct = plan.direct;
     hipStream_t st = (hipStream_t)stream;
     const size_t n_canon = (size_t)L * q + (size_t)L * (L - 1) / 2 * q * q;
     const size_t n_w4 = ((size_t)L * L * q + (size_t)L) * (QS / 4);

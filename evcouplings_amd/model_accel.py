@@ -14,6 +14,8 @@ for a block-wise one -- host-side format code, same attributes; measured to be n
 `plm_model_pair_scores`, `plm_double_mutants` and `plm_independent_fields`.  Off by default.
 `sample_sequences(model, n)` draws sequences from a model with the library's Gibbs sampler (`plm_sample`,
 DESIGN_NEXT_ROWS.md section 9.6); the reference has no sampler, so `install()` has nothing to rebind for it.
+`refine_model(model)` refines a model's fields and couplings towards its own `f_i`, `f_ij` with the library's
+Boltzmann-machine loop (`plm_bm_fit`, section 9.7), so that its samples reproduce those frequencies.
 """
 from copy import deepcopy
 
@@ -112,6 +114,38 @@ def sample_sequences(model, n_chains, burn_in=100, n_snapshots=1, thin=1, beta=1
     out = out.reshape(-1, L)
     res = letters[out] if as_letters else out
     return (res, en.reshape(-1, 3)) if energies else res
+
+
+def refine_model(model, n_chains=4096, n_epochs=120, sweeps_per_epoch=2, lr=0.5, lr_decay_after=None, lambda_h=None,
+                 lambda_j=None, tol=0.0, seed=0, start=None, first_epoch=0, callback=None, device=0):
+    """
+    Boltzmann-machine refinement (`plm.bm_fit`) of a pseudo-likelihood model towards its own frequencies.  `model` is a
+    `CouplingsModel` (`f_i`, `f_ij` and `J_ij` [L, L, q, q], `h_i`, `lambda_h`, `lambda_J`, `N_eff`) or the dict that
+    `model_io.read_model_file` returns.  The targets are the model's f_i, f_ij, the start point its h_i, J_ij.  The
+    regularisers default to the file's lambda_h / N_eff and lambda_J / N_eff (the plmc penalties on the per-sequence
+    scale of the frequencies); lr_decay_after defaults to half the epochs.  Returns the dict of `plm.bm_fit` (hi, and
+    jij as i<j blocks).
+    """
+    from evcouplings_amd import plm
+    if isinstance(model, dict):
+        fi, fij, hi, jij = model["fi"], model["fij"], model["hi"], model["jij"]
+        lam_h, lam_j, n_eff = model["lambda_h"], model["lambda_j"], model["n_eff"]
+    else:
+        fi, hi = np.asarray(model.f_i), np.asarray(model.h_i)
+        fij, jij = _pairs_from_dense(np.asarray(model.f_ij)), _pairs_from_dense(np.asarray(model.J_ij))
+        lam_h, lam_j, n_eff = model.lambda_h, model.lambda_J, model.N_eff
+    if (lambda_h is None or lambda_j is None) and not float(n_eff) > 0:
+        raise ValueError("the model has no N_eff > 0 to scale its regularisers by; pass lambda_h and lambda_j")
+    if lambda_h is None:
+        lambda_h = max(float(lam_h), 0.0) / float(n_eff)
+    if lambda_j is None:
+        lambda_j = max(float(lam_j), 0.0) / float(n_eff)
+    if lr_decay_after is None:
+        lr_decay_after = int(n_epochs) // 2
+    q = np.asarray(hi).shape[1]
+    return plm.bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=sweeps_per_epoch, lr=lr,
+                      lr_decay_after=lr_decay_after, lambda_h=lambda_h, lambda_j=lambda_j, tol=tol, seed=seed, start=start,
+                      first_epoch=first_epoch, callback=callback, device=device)
 
 
 def read_plmc_v2(self, f, precision):

@@ -202,6 +202,77 @@ def sample(hi, jij, q, n_chains, burn_in=10, n_snapshots=1, thin=1, beta=1.0, se
     return samples, en
 
 
+BM_STATUS = {_lib.STATUS_CONVERGED: "converged", _lib.STATUS_MAXITER: "maxiter", _lib.STATUS_INTERRUPTED: "interrupted"}
+
+
+def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, lr_decay_after=0, lambda_h=0.0,
+           lambda_j=0.0, tol=0.0, seed=0, start=None, first_epoch=0, callback=None, device=0):
+    """
+    Boltzmann-machine refinement of a Potts model (plm_bm_fit, DESIGN_NEXT_ROWS.md section 9.7): n_epochs steps of
+    x <- x + lr_g ((f - p) - 2 lambda x), where p are the one- and two-site frequencies of n_chains persistent Gibbs
+    chains after sweeps_per_epoch sweeps under the current x, and f = (fi, fij) are the targets.
+    fi: L x q; fij, jij: the i<j blocks [L(L-1)/2][q][q]; hi: L x q (the start point together with jij).  lambda_h,
+    lambda_j: per-sequence scale (the plmc value over N_eff).  lr_decay_after = T > 0: the step of global epoch g is
+    lr T / (g + 1) once g + 1 > T.  start: None (the sampler's start rule at the start point) or n_chains x L states;
+    first_epoch: the global number of the first epoch, for a call that continues an earlier one from its hi, jij and
+    chains.  tol > 0 stops before the update of the first epoch whose two maximal errors are <= tol; callback(epoch,
+    max_dfi, max_dfij, rms_dfij, lr) is called once per epoch and stops the fit by returning a true value.
+    Returns a dict: hi, jij, pi, pij, chains (int8 C x L), trace (one row per epoch that ran: max |fi - pi|,
+    max |fij - pij|, rms of fij - pij, lr_g), epochs_done (updates applied), status ("maxiter", "converged",
+    "interrupted").  The result is bitwise reproducible.
+    """
+    q, C_, E = int(q), int(n_chains), int(n_epochs)
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
+        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
+    L = hi.shape[0]
+    n_j = L * (L - 1) // 2 * q * q
+    jij = np.ascontiguousarray(jij, dtype=np.float32)
+    if jij.size != n_j:
+        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    fi = np.ascontiguousarray(fi, dtype=np.float32)
+    if fi.shape != (L, q):
+        raise ValueError("fi must be an (L, q) = (%d, %d) matrix" % (L, q))
+    fij = np.ascontiguousarray(fij, dtype=np.float32)
+    if fij.size != n_j:
+        raise ValueError("fij has %d entries, expected the %d i<j blocks of %d x %d" % (fij.size, L * (L - 1) // 2, q, q))
+    if C_ < 1 or E < 1 or int(sweeps_per_epoch) < 1 or int(first_epoch) < 0 or int(lr_decay_after) < 0:
+        raise ValueError("need n_chains >= 1, n_epochs >= 1, sweeps_per_epoch >= 1, first_epoch >= 0 and lr_decay_after >= 0")
+    for name, v in (("lr", lr), ("lambda_h", lambda_h), ("lambda_j", lambda_j), ("tol", tol)):
+        if not (float(v) >= 0.0 and np.isfinite(float(v))):
+            raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.int8)
+        if start.shape != (C_, L):
+            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
+    lib = _lib.load()
+    opts = _lib.PlmBmOpts(C_, E, int(sweeps_per_epoch), int(first_epoch), float(lr), int(lr_decay_after), float(lambda_h),
+                          float(lambda_j), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(start))
+    x = np.zeros(L * q + n_j, np.float32)
+    pi, pij = np.zeros((L, q), np.float32), np.zeros((L * (L - 1) // 2, q, q), np.float32)
+    chains = np.zeros((C_, L), np.int8)
+    trace = np.zeros((E, 4))
+    res = _lib.PlmBmResult(_ptr(x), _ptr(pi), _ptr(pij), _ptr(chains), _ptr(trace), 0, 0)
+    failure = []
+
+    def _cb(epoch, d_i, d_ij, rms, lr_g, _user):
+        try:
+            return 1 if callback(int(epoch), d_i, d_ij, rms, lr_g) else 0
+        except BaseException as exc:     # an exception must not cross the C frames
+            failure.append(exc)
+            return 1
+
+    cb = _lib.BM_EPOCH_CB(_cb) if callback is not None else _lib.BM_EPOCH_CB()
+    check(lib.plm_bm_fit(L, q, _ptr(fi), _ptr(fij), _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb,
+                         None, C.byref(res)))
+    if failure:
+        raise failure[0]
+    done = int(res.epochs_done)
+    rows = done if res.status == _lib.STATUS_MAXITER else done + 1
+    return dict(hi=x[:L * q].reshape(L, q).copy(), jij=x[L * q:].reshape(L * (L - 1) // 2, q, q).copy(), pi=pi, pij=pij,
+                chains=chains, trace=trace[:rows].copy(), epochs_done=done, status=BM_STATUS[int(res.status)])
+
+
 def single_mutant_matrix(target, q, hi, jij, device=0):
     """
     Energy differences of every single substitution of `target`: L x q x 3 float64 (dH, dH_J, dH_h), the

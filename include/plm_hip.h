@@ -313,6 +313,52 @@ typedef struct {
 int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_sample_opts *opts,
                int device, void *stream, int8_t *samples_out /* K x C x L */, double *energies_out /* K x C x 3 or NULL */);
 
+/* ---- Boltzmann-machine refinement of a model (DESIGN_NEXT_ROWS.md section 9.7) -------------------------------------
+ * Plain gradient ascent on the likelihood of target frequencies, the model's own marginals estimated by persistent Gibbs
+ * chains.  x_start: canonical parameters as for plm_hamiltonians; fi [L][q] and fij [L(L-1)/2][q][q] (pair blocks in the
+ * canonical order): the targets.  Chains begin at opts->start, or from the sampler's start rule at x_start.  Local epoch
+ * e = 0 .. n_epochs - 1, global epoch g = first_epoch + e:
+ *   1. the couplings are expanded as for plm_sample
+ *   2. every chain makes sweeps_per_epoch sweeps of plm_sample's contract (beta = 1, all states allowed, no fixed sites)
+ *      with the sweep indices g k .. g k + k - 1
+ *   3. exact int32 counts n_i(a), n_ij(a, b) over the chains; p = (float)n / (float)C
+ *   4. trace row e = (max |fi - pi|, max |fij - pij|, rms of fij - pij over all pair entries, lr_g) with lr_g = lr when
+ *      lr_decay_after == 0 or g + 1 <= lr_decay_after, else (float)((double)lr lr_decay_after / (g + 1))
+ *   5. tol > 0 and both maxima <= tol: stop before the update (PLM_STATUS_CONVERGED, epochs_done = e); the callback
+ *      returning non-zero stops the same way (PLM_STATUS_INTERRUPTED)
+ *   6. x <- x + lr_g ((f - p) - 2 lambda x) elementwise in float32 (lambda_h on fields, lambda_j on couplings; both on
+ *      the per-sequence scale, the plmc value over N_eff); lr_g == 0 leaves x as it is
+ * After n_epochs updates the status is PLM_STATUS_MAXITER.  The counts are integers, so the result is bitwise
+ * reproducible and depends on the arguments only.  Every output pointer may be NULL.  PLM_EINVAL: NULL arguments, sizes
+ * below 1, negative or non-finite lr, lambda_h, lambda_j or tol, start states outside 0..q-1, (first_epoch + n_epochs)
+ * sweeps_per_epoch at or above 2^32 - 1; PLM_EUNSUPPORTED: q outside 2..32; PLM_ENOMEM before any array is read. */
+typedef struct {
+    int32_t  n_chains;          /* C >= 1 persistent chains                                              */
+    int32_t  n_epochs;          /* E >= 1 epochs of this call                                            */
+    int32_t  sweeps_per_epoch;  /* k >= 1                                                                */
+    int32_t  first_epoch;       /* e0 >= 0: global number of this call's first epoch (continuation)      */
+    float    lr;                /* step, >= 0                                                            */
+    int32_t  lr_decay_after;    /* T >= 0: the step decays as T / (g + 1) after global epoch T - 1       */
+    float    lambda_h;          /* >= 0, per-sequence scale                                              */
+    float    lambda_j;          /* >= 0, per-sequence scale                                              */
+    float    tol;               /* >= 0; 0: never stop early                                             */
+    uint64_t seed;
+    const int8_t *start;        /* NULL, or C x L states                                                 */
+} plm_bm_opts;
+typedef struct {
+    float  *x_out;       /* canonical parameters after the last applied update                           */
+    float  *pi_out;      /* [L][q]            model frequencies of the last epoch that ran               */
+    float  *pij_out;     /* [L(L-1)/2][q][q]                                                             */
+    int8_t *chains_out;  /* C x L states of the last epoch that ran                                      */
+    double *trace;       /* n_epochs x 4, one row per epoch that ran                                     */
+    int32_t epochs_done; /* updates applied                                                              */
+    int32_t status;      /* PLM_STATUS_MAXITER, PLM_STATUS_CONVERGED or PLM_STATUS_INTERRUPTED           */
+} plm_bm_result;
+/* Called once per epoch after its trace row is known and before its update, with the global epoch number. */
+typedef int (*plm_bm_epoch_cb)(int32_t epoch, double max_dfi, double max_dfij, double rms_dfij, double lr, void *user);
+int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *fij, const float *x_start,
+               const plm_bm_opts *opts, int device, void *stream, plm_bm_epoch_cb cb, void *user, plm_bm_result *result);
+
 /* ---- mean-field direct coupling analysis ---------------------------
  * Replaces the arithmetic of evcouplings/couplings/mean_field.py:163-222 (MeanFieldDCA.fit: weights,
  * frequencies, pseudo-count regularisation :717-790, covariance matrix :897-940, J = -C^-1 :204-210 and
