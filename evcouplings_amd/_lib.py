@@ -65,6 +65,13 @@ class PlmSampleOpts(C.Structure):
     ]
 
 
+class PlmSamplePlanInfo(C.Structure):
+    _fields_ = [
+        ("direct", C.c_int32), ("tile", C.c_int32), ("jc", C.c_int32), ("nv", C.c_int32), ("n_workgroups", C.c_int32),
+        ("lds_bytes", C.c_int64),
+    ]
+
+
 class PlmBmOpts(C.Structure):
     _fields_ = [
         ("n_chains", C.c_int32), ("n_epochs", C.c_int32), ("sweeps_per_epoch", C.c_int32), ("first_epoch", C.c_int32),
@@ -112,6 +119,7 @@ SYMBOLS = [
     ("plm_double_mutants", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),
     ("plm_independent_fields", C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P, _P, _P]),
     ("plm_sample", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmSampleOpts), C.c_int, _P, _P, _P]),
+    ("plm_sample_plan", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmSamplePlanInfo)]),
     ("plm_bm_fit", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(PlmBmOpts), C.c_int, _P, BM_EPOCH_CB, _P,
                              C.POINTER(PlmBmResult)]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,

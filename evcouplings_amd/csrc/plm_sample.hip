@@ -81,6 +81,14 @@ __global__ __launch_bounds__(256) void k_sample_expand(const float *__restrict__
     W[t] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// u = ((word0 >> 8) + 0.5) 2^-24 in float32, kept below 1: above 2^23 the sum rounds to an integer (ties to even), and
+// for the one word in 2^24 with all 24 bits set it rounds to 2^24, u = 1, where no running sum exceeds u S_last and the
+// draw would fall through to the last allowed state whatever its weight.  That word takes the largest float32 below 1;
+// u S < S then holds for every S, so the first state with S_a > u S_last always exists.
+__device__ __forceinline__ float uniform24(uint32_t word0) {
+    return fminf(__fmul_rn((float)(word0 >> 8) + 0.5f, 5.9604644775390625e-08f), 0.99999994f);
+}
+
 // One draw of the contract: e_a = exp(beta U_a - max) over the allowed states in state order, running sum S_a, the new
 // state is the first allowed a with S_a > u S_last (the last allowed state if none).  U holds NV float4 (states a >= q
 // are padding).  u = ((word0 >> 8) + 0.5) 2^-24.
@@ -105,7 +113,7 @@ __device__ __forceinline__ int draw_state(const float4 *U, int q, uint32_t allow
         S += on ? expf(__fsub_rn(e[a], m)) : 0.f;
         e[a] = S;                                   // the running sum; flat across states that are not allowed
     }
-    const float u = __fmul_rn((float)(word0 >> 8) + 0.5f, 5.9604644775390625e-08f);
+    const float u = uniform24(word0);
     const float t = __fmul_rn(u, S);
     int pick = -1, last = 0;
 #pragma unroll
@@ -269,7 +277,7 @@ __device__ __forceinline__ int draw_group(float U, int a, int q, uint32_t allowe
     const int base = (threadIdx.x & 63) & ~(QP - 1);
     float S = 0.f;
     for (int b = 0; b < q; b++) S += __shfl(e, base + b, 64);
-    const float u = __fmul_rn((float)(word0 >> 8) + 0.5f, 5.9604644775390625e-08f);
+    const float u = uniform24(word0);
     const float t = __fmul_rn(u, S);
     int pick = -1, last = 0;
     S = 0.f;
@@ -354,43 +362,40 @@ __global__ void k_field_energy(const float *__restrict__ h, const int8_t *__rest
 
 typedef gibbs::SweepPlan Plan;
 
+// The planner's own checks of one (tile, j-chunk): a chunk is at most GS_PF float4 per thread, and the two staging
+// buffers and the chain states fit the LDS of a CU.  Nothing that fails them is ever launched.
+bool tiled_fits(int L, int q, int tile, int JC, Plan *p) {
+    if ((size_t)JC * q * p->NV > (size_t)GS_PF * tile) return false;
+    const size_t lds = 2 * (size_t)JC * q * p->NVP * 16 + (size_t)((L + 3) / 4) * tile * 4;
+    if (lds > GS_LDS_BYTES) return false;
+    p->tile = tile;
+    p->JC = JC;
+    p->lds = lds;
+    return true;
+}
+
 // tile of chains per workgroup, j-chunk and LDS size: the largest tile that still gives every CU a workgroup, limited
-// by what the chain states leave of the LDS
-bool make_plan(int L, int q, int C, int n_cu, Plan *out) {
+// by what the chain states leave of the LDS.  force_tile / force_jc != 0 (PLM_SAMPLE_TILE / PLM_SAMPLE_JC) replace the
+// two preferences -- the spread over the CUs, and no chunk of 2 L sites or more -- and none of the checks.
+bool make_plan(int L, int q, int C, int n_cu, int force_tile, int force_jc, Plan *out) {
     Plan p = {};
     p.NV = (q + 3) / 4;
     p.NVP = (p.NV % 2 == 0) ? p.NV + 1 : p.NV;
-    const int L4 = (L + 3) / 4;
     const int tiles[3] = {256, 128, 64};
     const int cands[6] = {16, 12, 8, 4, 2, 1};
     for (int t = 0; t < 3; t++) {
-        p.tile = tiles[t];
-        if (t < 2 && (C + p.tile - 1) / p.tile < n_cu) continue;          // spread small calls over the CUs
-        const size_t xs = (size_t)L4 * p.tile * 4;
-        for (int c = 0; c < 6 && (p.JC = cands[c]); c++) {
-            if (p.JC > 1 && p.JC >= 2 * L) continue;
-            if ((size_t)p.JC * q * p.NV > (size_t)GS_PF * p.tile) continue;  // a chunk is GS_PF float4 per thread
-            p.lds = 2 * (size_t)p.JC * q * p.NVP * 16 + xs;
-            if (p.lds <= GS_LDS_BYTES) {
+        const int tile = tiles[t];
+        if (force_tile ? tile != force_tile : (t < 2 && (C + tile - 1) / tile < n_cu)) continue;   // spread small calls over the CUs
+        for (int c = 0; c < 6; c++) {
+            const int JC = cands[c];
+            if (force_jc ? JC != force_jc : (JC > 1 && JC >= 2 * L)) continue;
+            if (tiled_fits(L, q, tile, JC, &p)) {
                 *out = p;
                 return true;
             }
         }
     }
-    // the smaller tiles, whatever the CU count
-    for (int t = 1; t < 3; t++) {
-        p.tile = tiles[t];
-        const size_t xs = (size_t)L4 * p.tile * 4;
-        for (int c = 0; c < 6 && (p.JC = cands[c]); c++) {
-            if ((size_t)p.JC * q * p.NV > (size_t)GS_PF * p.tile) continue;
-            p.lds = 2 * (size_t)p.JC * q * p.NVP * 16 + xs;
-            if (p.lds <= GS_LDS_BYTES) {
-                *out = p;
-                return true;
-            }
-        }
-    }
-    return false;
+    return false;       // tile 64 with JC = 1 is the smallest plan there is: no other tile or chunk fits either
 }
 
 template <int NV, int TILE>
@@ -432,7 +437,7 @@ template <int QP>
 hipError_t launch_direct_t(hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src, const uint8_t *fixed,
                            uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps, int8_t *dst) {
     constexpr int CPW = 256 / QP;
-    const size_t lds = (size_t)CPW * ((L + 3) / 4 * 4);
+    const size_t lds = (size_t)CPW * ((L + 3) / 4 * 4);     // direct_lds(L, q): QP = direct_group(L, q)
     auto kern = k_gibbs_direct<QP>;
     hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -442,18 +447,73 @@ hipError_t launch_direct_t(hipStream_t st, const float4 *W, int L, int q, int C,
     return hipGetLastError();
 }
 
-int direct_group(int q) { return q <= 2 ? 2 : q <= 4 ? 4 : q <= 8 ? 8 : q <= 16 ? 16 : 32; }
-bool direct_fits(int L, int q) { return (size_t)(256 / direct_group(q)) * ((L + 3) / 4 * 4) <= GS_LDS_BYTES; }
+// lanes per chain of the direct form: the power of two >= q, and a larger one (fewer chains per workgroup, the lanes
+// a >= q idle) where the states of that many chains would not fit the LDS
+int direct_group(int L, int q) {
+    int g = q <= 2 ? 2 : q <= 4 ? 4 : q <= 8 ? 8 : q <= 16 ? 16 : 32;
+    while (g < 32 && (size_t)(256 / g) * ((L + 3) / 4 * 4) > GS_LDS_BYTES) g *= 2;
+    return g;
+}
+size_t direct_lds(int L, int q) { return (size_t)(256 / direct_group(L, q)) * ((L + 3) / 4 * 4); }
+bool direct_fits(int L, int q) { return direct_lds(L, q) <= GS_LDS_BYTES; }
 
 hipError_t launch_direct(hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src, const uint8_t *fixed,
                          uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps, int8_t *dst) {
-    switch (direct_group(q)) {
+    switch (direct_group(L, q)) {
     case 2: return launch_direct_t<2>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
     case 4: return launch_direct_t<4>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
     case 8: return launch_direct_t<8>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
     case 16: return launch_direct_t<16>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
     default: return launch_direct_t<32>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
     }
+}
+
+// 0: the variable is not set; -1: it is set to something else than one of the values
+int env_choice(const char *name, const int *values, int n) {
+    const char *v = getenv(name);
+    if (!v || !*v) return 0;
+    char *end = nullptr;
+    const long x = strtol(v, &end, 10);
+    if (*end) return -1;
+    for (int k = 0; k < n; k++)
+        if (x == values[k]) return values[k];
+    return -1;
+}
+
+// The one place a plan is made: plm_sample and plm_bm_fit (through gibbs::plan_sweeps) and plm_sample_plan.  Host code.
+int choose_plan(int L, int q, int C, int n_cu, Plan *out) {
+    static const int tiles[3] = {64, 128, 256}, chunks[6] = {1, 2, 4, 8, 12, 16};
+    const int force_tile = env_choice("PLM_SAMPLE_TILE", tiles, 3), force_jc = env_choice("PLM_SAMPLE_JC", chunks, 6);
+    if (force_tile < 0) return plm_fail(PLM_EINVAL, "PLM_SAMPLE_TILE must be 64, 128 or 256 (got '%s')", getenv("PLM_SAMPLE_TILE"));
+    if (force_jc < 0) return plm_fail(PLM_EINVAL, "PLM_SAMPLE_JC must be 1, 2, 4, 8, 12 or 16 (got '%s')", getenv("PLM_SAMPLE_JC"));
+    // the tiled form wherever the chain states fit the LDS; the direct form for longer models, or on request
+    // (PLM_SAMPLE_FORM=direct | tiled, measurements only: the two forms return the same states).  PLM_SAMPLE_TILE and
+    // PLM_SAMPLE_JC (measurements and tests only) choose among the plans of the tiled form and say nothing when the
+    // direct form is asked for.
+    const char *form = getenv("PLM_SAMPLE_FORM");
+    bool direct = form && !strcmp(form, "direct");
+    Plan plan = {};
+    if (!direct && !make_plan(L, q, C, n_cu, force_tile, force_jc, &plan)) {
+        if (force_tile || force_jc)
+            return plm_fail(PLM_EINVAL, "%s%s%s: no such plan for %d sites with %d states (a chunk needs JC q ceil(q/4) <= %d x tile "
+                                        "and the workgroup at most %d bytes of LDS)", force_tile ? "PLM_SAMPLE_TILE" : "",
+                            force_tile && force_jc ? " with " : "", force_jc ? "PLM_SAMPLE_JC" : "", L, q, GS_PF, GS_LDS_BYTES);
+        if (form && !strcmp(form, "tiled"))
+            return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
+        direct = true;
+    }
+    if (direct) {
+        if (!direct_fits(L, q))
+            return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
+        plan = Plan{};
+        plan.NV = (q + 3) / 4;
+        plan.NVP = (plan.NV % 2 == 0) ? plan.NV + 1 : plan.NV;
+        plan.tile = 256 / direct_group(L, q);      // chains per workgroup
+        plan.lds = direct_lds(L, q);
+    }
+    plan.direct = direct;
+    *out = plan;
+    return PLM_OK;
 }
 
 }  // namespace
@@ -463,18 +523,7 @@ namespace gibbs {
 int plan_sweeps(int L, int q, int C, int device, SweepPlan *out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDeviceProperties failed");
-    Plan plan = {};
-    // the tiled form wherever the chain states fit the LDS; the direct form for longer models, or on request
-    // (PLM_SAMPLE_FORM=direct | tiled, measurements only: the two forms return the same states)
-    const char *form = getenv("PLM_SAMPLE_FORM");
-    bool direct = form && !strcmp(form, "direct");
-    const bool tiled_fits = make_plan(L, q, C, prop.multiProcessorCount, &plan);
-    if (!tiled_fits && !(form && !strcmp(form, "tiled"))) direct = true;
-    if (direct ? !direct_fits(L, q) : !tiled_fits)
-        return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
-    plan.direct = direct;
-    *out = plan;
-    return PLM_OK;
+    return choose_plan(L, q, C, prop.multiProcessorCount, out);
 }
 
 size_t table_float4(int L, int q) { return ((size_t)L * L * q + (size_t)L) * ((q + 3) / 4); }
@@ -494,6 +543,31 @@ hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, in
 }
 
 }  // namespace gibbs
+
+int plm_sample_plan(int32_t n_sites, int32_t n_states, int32_t n_chains, int32_t n_cu, plm_sample_plan_info *out) {
+    if (!out) return plm_fail(PLM_EINVAL, "NULL plan");
+    if (n_sites < 1 || n_chains < 1)
+        return plm_fail(PLM_EINVAL, "need n_sites >= 1 and n_chains >= 1 (got %d, %d)", n_sites, n_chains);
+    if (n_states < 2 || n_states > GS_Q)
+        return plm_fail(PLM_EUNSUPPORTED, "the sampler supports 2..32 states (got %d)", n_states);
+    Plan plan;
+    int rc;
+    if (n_cu > 0) {
+        rc = choose_plan(n_sites, n_states, n_chains, n_cu, &plan);      // no device, no HIP call
+    } else {
+        int device = 0;
+        if (hipGetDevice(&device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDevice failed");
+        rc = gibbs::plan_sweeps(n_sites, n_states, n_chains, device, &plan);
+    }
+    if (rc) return rc;
+    out->direct = plan.direct ? 1 : 0;
+    out->tile = plan.tile;
+    out->jc = plan.direct ? 0 : plan.JC;
+    out->nv = plan.NV;
+    out->n_workgroups = (n_chains + plan.tile - 1) / plan.tile;
+    out->lds_bytes = (int64_t)plan.lds;
+    return PLM_OK;
+}
 
 int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_sample_opts *opts, int device,
                void *stream, int8_t *samples_out, double *energies_out) {

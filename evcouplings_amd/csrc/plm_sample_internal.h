@@ -12,7 +12,8 @@ struct SweepPlan {
     bool direct;                // the direct form instead
 };
 
-// PLM_OK and the plan, or PLM_EDEVICE / PLM_EUNSUPPORTED with the message recorded
+// PLM_OK and the plan, or PLM_EDEVICE / PLM_EUNSUPPORTED / PLM_EINVAL (a PLM_SAMPLE_TILE or PLM_SAMPLE_JC without a
+// valid plan) with the message recorded
 int plan_sweeps(int L, int q, int C, int device, SweepPlan *out);
 
 size_t table_float4(int L, int q);       // float4 of the expanded table (couplings and fields)

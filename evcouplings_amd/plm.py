@@ -202,6 +202,20 @@ def sample(hi, jij, q, n_chains, burn_in=10, n_snapshots=1, thin=1, beta=1.0, se
     return samples, en
 
 
+def sample_plan(L, q, n_chains, n_cu=0):
+    """
+    The launch plan `sample` and `bm_fit` use for L sites, q states and n_chains chains (plm_sample_plan,
+    DESIGN_NEXT_ROWS.md section 9.6) on a device with n_cu compute units; n_cu = 0: the current device.  With n_cu > 0
+    no device is needed.  Returns a dict: direct (bool), tile (chains per workgroup), jc (sites per staged chunk, 0 for
+    the direct form), nv (ceil(q / 4)), n_workgroups, lds_bytes.  PLM_SAMPLE_FORM, PLM_SAMPLE_TILE and PLM_SAMPLE_JC
+    are honoured as the sampler honours them.
+    """
+    info = _lib.PlmSamplePlanInfo()
+    check(_lib.load().plm_sample_plan(int(L), int(q), int(n_chains), int(n_cu), C.byref(info)))
+    return dict(direct=bool(info.direct), tile=int(info.tile), jc=int(info.jc), nv=int(info.nv),
+                n_workgroups=int(info.n_workgroups), lds_bytes=int(info.lds_bytes))
+
+
 BM_STATUS = {_lib.STATUS_CONVERGED: "converged", _lib.STATUS_MAXITER: "maxiter", _lib.STATUS_INTERRUPTED: "interrupted"}
 
 

@@ -288,13 +288,13 @@ int plm_independent_fields(const double *fi, int32_t n_sites, int32_t n_states, 
  * (its loops stop at _hamiltonians / _delta_hamiltonian, couplings/model.py:25-177).  C independent chains; one sweep
  * visits the sites 0 .. L-1 in that order and draws x_ci ~ softmax_a beta (h_i(a) + sum_{j != i} J_ij(a, x_cj)) over the
  * allowed states; fixed sites are skipped.  Random numbers: Philox4x32-10, counter (chain, 0, sweep, site), key (seed low,
- * seed high); sweep counts from 0 across burn-in, thinning and snapshots; u = ((word0 >> 8) + 0.5) 2^-24; with
+ * seed high); sweep counts from 0 across burn-in, thinning and snapshots; u = ((word0 >> 8) + 0.5) 2^-24 (below 1 in float32 too); with
  * e_a = exp(beta U_a - max) over the allowed states in state order and running sum S_a the new state is the first allowed
  * a with S_a > u S_last.  start == NULL: chain c starts from one such draw per site of softmax beta h_i with sweep index
  * 0xFFFFFFFF.  U accumulates in float32 over j = 0 .. L-1.  The result depends on (seed, chain index, model, options)
  * only: not on n_chains, the device or the run.
- * x_canonical: as plm_hamiltonians (q in 2..32, else PLM_EUNSUPPORTED; any n_sites >= 1 whose chain states fit the LDS,
- * about 2 400).  samples_out: K x C x L states; energies_out: K x C x 3 doubles (H, H_J, H_h) of the snapshots at beta = 1,
+ * x_canonical: as plm_hamiltonians (q in 2..32, else PLM_EUNSUPPORTED; any n_sites >= 1 whose chain states fit the LDS:
+ * 20 480, the tiled form up to about 2 500 and the slower direct form beyond, see plm_sample_plan).  samples_out: K x C x L states; energies_out: K x C x 3 doubles (H, H_J, H_h) of the snapshots at beta = 1,
  * what plm_hamiltonians returns for those rows, or NULL.  PLM_ENOMEM before any allocation, and before any array is
  * read, when the device cannot hold the expanded couplings (L^2 q ceil4(q) floats), the chain states and the outputs.
  * PLM_EINVAL: start states outside 0..q-1, or not allowed at a site that is not fixed; no allowed state; beta not
@@ -312,6 +312,24 @@ typedef struct {
 } plm_sample_opts;
 int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_sample_opts *opts,
                int device, void *stream, int8_t *samples_out /* K x C x L */, double *energies_out /* K x C x 3 or NULL */);
+
+/* The launch plan plm_sample and plm_bm_fit choose for a shape: which form of the sweep, and for the tiled form the tile
+ * of chains per workgroup and the chunk of sites staged in LDS at a time.  n_cu > 0: the plan on a device with that many
+ * compute units, pure host code (no device is needed); n_cu <= 0: on the current device.  For the direct form `tile` is
+ * the chains per workgroup (256 / group size, the group being the power of two >= q, at least 2) and jc is 0.  The
+ * environment variables PLM_SAMPLE_FORM=tiled|direct, PLM_SAMPLE_TILE=64|128|256 and PLM_SAMPLE_JC=1|2|4|8|12|16
+ * (measurements and tests only; every plan returns the same states) are honoured as the two calls honour them: a tile or
+ * chunk whose plan fails the planner's checks (jc q nv <= 8 tile, lds_bytes <= 163840) is PLM_EINVAL, never launched.
+ * PLM_EUNSUPPORTED: q outside 2..32, or no form holds the chain states of a workgroup in LDS. */
+typedef struct {
+    int32_t direct;        /* 1: the direct form (lanes = chain x state), 0: the tiled form            */
+    int32_t tile;          /* chains per workgroup                                                      */
+    int32_t jc;            /* sites per staged chunk (tiled form)                                       */
+    int32_t nv;            /* ceil(q / 4): float4 per row of the expanded couplings                     */
+    int32_t n_workgroups;  /* ceil(n_chains / tile)                                                     */
+    int64_t lds_bytes;     /* dynamic LDS of a workgroup                                                */
+} plm_sample_plan_info;
+int plm_sample_plan(int32_t n_sites, int32_t n_states, int32_t n_chains, int32_t n_cu, plm_sample_plan_info *out);
 
 /* ---- Boltzmann-machine refinement of a model (DESIGN_NEXT_ROWS.md section 9.7) -------------------------------------
  * Plain gradient ascent on the likelihood of target frequencies, the model's own marginals estimated by persistent Gibbs

@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bm_twin as bt  # noqa: E402
+import sampler_plan_cases as cases  # noqa: E402
 from evcouplings_amd import _lib, model_io, plm  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -18,6 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN_MODEL = os.path.join(HERE, "golden", "hip_fit_L24.model")
 GOLDEN_NPZ = os.path.join(HERE, "golden", "hip_fit_L24.npz")
 SHAPES = [(24, 21, 4096), (300, 21, 512), (45, 32, 2048), (17, 2, 4096), (64, 5, 1000)]
+# the edges of k_bm_transpose / k_bm_count: chain counts that are no multiple of 4 (padding chains in the last word),
+# fewer than 4 chains, 1251 chain words over five slices of 251 (the last holds 247), q > 22 (8 sites per workgroup),
+# and one site (no pair, fij and J empty)
+SHAPES += [(70, 5, 333), (33, 21, 1023), (17, 32, 1021), (6, 4, 5001), (3, 2, 1), (2, 3, 5), (1, 7, 1000)]
 
 
 def _case(L, q, Cn):
@@ -55,11 +60,11 @@ def test_one_epoch_is_the_sampler_the_counts_and_the_step(L, q, Cn):
     for p, n in ((res["pi"], ni), (res["pij"], nij)):
         exact = n.astype(np.float64) / Cn
         assert (np.abs(p.astype(np.float64) - exact) <= np.spacing(exact.astype(np.float32))).all()
-    bound = 2.0 ** -22 * max(1.0, float(np.abs(h).max()), float(np.abs(J).max()))
+    bound = 2.0 ** -22 * max(1.0, float(np.abs(h).max()), float(np.abs(J).max(initial=0.0)))      # J is empty at L = 1
     for got, x, f, p, lam in ((res["hi"], h, fi, res["pi"], lam_h), (res["jij"], J, fij, res["pij"], lam_j)):
         x, f, p = (a.astype(np.float64) for a in (x, f, p))
         want = x + lr * ((f - p) - 2.0 * np.float64(np.float32(lam)) * x)
-        err = float(np.abs(got.astype(np.float64) - want).max())
+        err = float(np.abs(got.astype(np.float64) - want).max(initial=0.0))
         print("L=%d q=%d: max |x_out - step 6| = %.3g (bound %.3g)" % (L, q, err, bound))
         assert err <= bound
     row = bt.trace_row(fi, fij, res["pi"], res["pij"], lr)
@@ -93,6 +98,61 @@ def test_continuation_and_repetition_are_bitwise(L, q, Cn):
     assert whole["trace"][2:].tobytes() == second["trace"].tobytes()
     assert whole["trace"][:, 3].tolist() == [float(np.float32(0.5 / (g + 1))) for g in range(4)]
     assert not np.array_equal(whole["hi"], first["hi"])
+
+
+@pytest.mark.parametrize("L,q,Cn", [(6, 4, 5001), (33, 21, 1023)])
+def test_every_chain_in_one_bin(L, q, Cn):
+    """h_i(a_i) = 40 for one state per site, J = 0: every draw gives a_i (the other states weigh e^-40 against a u of
+    at least 2^-25), so all C increments of a histogram land on one LDS bin, and at (6, 4, 5001) the five chain slices
+    add to one global bin.  The targets are multiples of 2^-8 (fi) and 2^-16 (fij): every (f - p)^2 is a multiple of
+    2^-32 and their sum stays below 2^18, exact in float64 in any order, so the whole trace row is the twin's.
+    (At (33, 21, 1023) chain 722 meets, at site 32 of sweep 0, the one random word in 2^24 whose u rounds to 1 in
+    float32: the draw that used to fall through to the last state, tests/test_gpu_sampler_plans.py.)"""
+    rng = np.random.default_rng(4000 + L)
+    a = rng.integers(0, q, size=L)
+    h = np.zeros((L, q), np.float32)
+    h[np.arange(L), a] = 40.0
+    J = np.zeros((L * (L - 1) // 2, q, q), np.float32)
+    fi = (np.rint(rng.dirichlet(np.ones(q), size=L) * 256) / 256).astype(np.float32)
+    fij = (fi[:, None, :, None] * fi[None, :, None, :])[np.triu_indices(L, 1)].astype(np.float32)
+    x0 = rng.integers(0, q, size=(Cn, L)).astype(np.int8)
+    res = plm.bm_fit(fi, fij, q, h, J, Cn, 2, sweeps_per_epoch=1, lr=0.0, seed=9, start=x0)
+    assert res["epochs_done"] == 2 and res["trace"].shape == (2, 4)
+    assert np.array_equal(res["chains"], np.tile(a.astype(np.int8), (Cn, 1)))
+    pi = np.zeros((L, q), np.float32)
+    pi[np.arange(L), a] = 1.0
+    iu, ju = np.triu_indices(L, 1)
+    pij = np.zeros((len(iu), q, q), np.float32)
+    pij[np.arange(len(iu)), a[iu], a[ju]] = 1.0
+    assert res["pi"].tobytes() == pi.tobytes() and res["pij"].tobytes() == pij.tobytes()
+    assert res["hi"].tobytes() == h.tobytes() and res["jij"].tobytes() == J.tobytes()
+    row = bt.trace_row(fi, fij, pi, pij, 0.0)
+    assert res["trace"][0].tolist() == row and res["trace"][1].tolist() == row, (res["trace"], row)
+    # the same from the start rule
+    res = plm.bm_fit(fi, fij, q, h, J, Cn, 1, sweeps_per_epoch=1, lr=0.0, seed=9)
+    assert np.array_equal(res["chains"], np.tile(a.astype(np.int8), (Cn, 1)))
+    assert res["pi"].tobytes() == pi.tobytes() and res["pij"].tobytes() == pij.tobytes()
+
+
+def test_forced_tiles_give_the_chains_of_tile_64():
+    """plm_bm_fit plans its sweeps where plm_sample does: under PLM_SAMPLE_TILE both run k_gibbs<6, 128> and <6, 256>,
+    and the chains are those of the tile the planner picks for 300 chains."""
+    L, q, Cn = 24, 21, 300
+    h, J, fi, fij, x0 = _case(L, q, Cn)
+    kw = dict(sweeps_per_epoch=2, lr=0.5, lambda_h=0.01, lambda_j=0.02, seed=41, start=x0)
+    with cases.forced():
+        assert plm.sample_plan(L, q, Cn)["tile"] == 64
+        base = plm.bm_fit(fi, fij, q, h, J, Cn, 2, **kw)
+        ref, _ = plm.sample(h, J, q, Cn, burn_in=2, seed=41, start=x0, energies=False)
+    for tile in (128, 256):
+        with cases.forced(tile=tile):
+            p = plm.sample_plan(L, q, Cn)
+            assert (p["direct"], p["tile"], p["n_workgroups"]) == (False, tile, -(-Cn // tile))
+            one = plm.bm_fit(fi, fij, q, h, J, Cn, 1, **kw)
+            smp, _ = plm.sample(h, J, q, Cn, burn_in=2, seed=41, start=x0, energies=False)
+            two = plm.bm_fit(fi, fij, q, h, J, Cn, 2, **kw)
+        assert np.array_equal(one["chains"], smp[0]) and np.array_equal(smp[0], ref[0])
+        _same(two, base)
 
 
 def test_start_rule_is_the_samplers():
