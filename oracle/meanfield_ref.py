@@ -62,7 +62,8 @@ def mean_field(fi, fij_pairs, pseudo_count=0.5, want_di=True):
     return out
 
 
-def direct_information(J, rfi):
+def direct_information(J, rfi, trace=None):
+    """trace, if given, is called as trace(i, j, diff) after every update of a pair's fixed-point iteration"""
     L, q = rfi.shape
     di = np.zeros((L, L))
     for i in range(L - 1):
@@ -77,6 +78,8 @@ def direct_information(J, rfi):
                 uj = rfi[j] / (hti @ W)
                 uj /= uj.sum()
                 diff = max(np.abs(ui - hti).max(), np.abs(uj - htj).max())
+                if trace is not None:
+                    trace(i, j, diff)
                 hti, htj = ui, uj
             P = W * np.outer(hti, htj)
             P /= P.sum()
