@@ -89,6 +89,24 @@ class PlmBmResult(C.Structure):
 
 BM_EPOCH_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
 
+
+class PlmAisOpts(C.Structure):
+    _fields_ = [
+        ("n_chains", C.c_int32), ("n_temps", C.c_int32), ("sweeps_per_temp", C.c_int32), ("steps_per_launch", C.c_int32),
+        ("betas", C.c_void_p), ("seed", C.c_uint64),
+    ]
+
+
+class PlmAisResult(C.Structure):
+    _fields_ = [
+        ("log_z", C.c_double), ("log_z0", C.c_double), ("log_z_se", C.c_double), ("ess", C.c_double),
+        ("log_w", C.c_void_p), ("e_j", C.c_void_p), ("states", C.c_void_p),
+        ("steps_done", C.c_int32), ("status", C.c_int32),
+    ]
+
+
+AIS_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -122,6 +140,8 @@ SYMBOLS = [
     ("plm_sample_plan", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmSamplePlanInfo)]),
     ("plm_bm_fit", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(PlmBmOpts), C.c_int, _P, BM_EPOCH_CB, _P,
                              C.POINTER(PlmBmResult)]),
+    ("plm_ais", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmAisOpts), C.c_int, _P, AIS_CB, _P,
+                          C.POINTER(PlmAisResult)]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),

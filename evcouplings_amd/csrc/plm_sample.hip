@@ -11,6 +11,7 @@
 //   k_field_energy   (H, H_J, H_h) of the field-only model (L = 1), which the forward GEMM of plm_hamiltonians cannot take
 #include "../../include/plm_hip.h"
 #include "plm_sample_internal.h"
+#include "plm_gibbs_device.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -22,29 +23,6 @@ int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the mes
 int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
 
 namespace {
-
-#define GS_Q 32                 // largest alphabet
-#define GS_PF 8                 // float4 of a W chunk one thread carries from global memory to LDS
-#define GS_DEPTH 3              // chunks in flight per thread (the three register sets of k_gibbs)
-#define GS_LDS_BYTES 163840     // LDS of a CU
-#define GS_START_SWEEP 0xFFFFFFFFu
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11); only word 0 of the block is used
-__device__ __forceinline__ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                 uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
 
 __device__ __forceinline__ int64_t pair_index(int i, int j, int L) {   // i < j, row-major
     return (int64_t)i * (2 * L - i - 1) / 2 + (j - i - 1);
@@ -80,109 +58,6 @@ __global__ __launch_bounds__(256) void k_sample_expand(const float *__restrict__
     }
     W[t] = make_float4(v[0], v[1], v[2], v[3]);
 }
-
-// u = ((word0 >> 8) + 0.5) 2^-24 in float32, kept below 1: above 2^23 the sum rounds to an integer (ties to even), and
-// for the one word in 2^24 with all 24 bits set it rounds to 2^24, u = 1, where no running sum exceeds u S_last and the
-// draw would fall through to the last allowed state whatever its weight.  That word takes the largest float32 below 1;
-// u S < S then holds for every S, so the first state with S_a > u S_last always exists.
-__device__ __forceinline__ float uniform24(uint32_t word0) {
-    return fminf(__fmul_rn((float)(word0 >> 8) + 0.5f, 5.9604644775390625e-08f), 0.99999994f);
-}
-
-// One draw of the contract: e_a = exp(beta U_a - max) over the allowed states in state order, running sum S_a, the new
-// state is the first allowed a with S_a > u S_last (the last allowed state if none).  U holds NV float4 (states a >= q
-// are padding).  u = ((word0 >> 8) + 0.5) 2^-24.
-template <int NV>
-__device__ __forceinline__ int draw_state(const float4 *U, int q, uint32_t allowed, float beta, uint32_t word0) {
-    float e[NV * 4];
-    float m = -INFINITY;
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-        e[4 * v + 0] = __fmul_rn(beta, U[v].x);
-        e[4 * v + 1] = __fmul_rn(beta, U[v].y);
-        e[4 * v + 2] = __fmul_rn(beta, U[v].z);
-        e[4 * v + 3] = __fmul_rn(beta, U[v].w);
-    }
-#pragma unroll
-    for (int a = 0; a < NV * 4; a++)
-        if (a < q && ((allowed >> a) & 1u)) m = fmaxf(m, e[a]);
-    float S = 0.f;
-#pragma unroll
-    for (int a = 0; a < NV * 4; a++) {
-        const bool on = a < q && ((allowed >> a) & 1u);
-        S += on ? expf(__fsub_rn(e[a], m)) : 0.f;
-        e[a] = S;                                   // the running sum; flat across states that are not allowed
-    }
-    const float u = uniform24(word0);
-    const float t = __fmul_rn(u, S);
-    int pick = -1, last = 0;
-#pragma unroll
-    for (int a = 0; a < NV * 4; a++) {
-        const bool on = a < q && ((allowed >> a) & 1u);
-        if (on) last = a;
-        if (on && pick < 0 && e[a] > t) pick = a;
-    }
-    return pick < 0 ? last : pick;
-}
-
-// The two steps of the pipeline as macros over register sets with named members.  The members are native vectors: a
-// float4 (a struct) is assigned between address spaces by memcpy, which kept the sets in scratch memory, with a wait
-// after every load.
-typedef float gs_f4 __attribute__((ext_vector_type(4)));
-struct PreSet { gs_f4 a0, a1, a2, a3, a4, a5, a6, a7; };    // GS_PF float4
-#define GS_FOR_P(X, pr) X(0, pr) X(1, pr) X(2, pr) X(3, pr) X(4, pr) X(5, pr) X(6, pr) X(7, pr)
-#define GS_LOAD_P(p, pr) pr.a##p = ((const gs_f4 *)src4)[min(tid + p * TILE, n4 - 1)];   /* past the chunk: a copy that is not stored */
-#define GS_STORE_P(p, pr) { const int k = tid + p * TILE; if (k < n4) ((gs_f4 *)buf)[(k / NV) * NVP + (k % NV)] = pr.a##p; }
-#define GS_FETCH(ch_, pr) do { \
-                if ((ch_) < n_chunks) { \
-                    const int n4 = (min(L, ((ch_) + 1) * JC) - (ch_) * JC) * row4; \
-                    const float4 *src4 = Wi + (int64_t)(ch_) * JC * row4; \
-                    GS_FOR_P(GS_LOAD_P, pr) \
-                } \
-    } while (0)
-#define GS_STEP(ch_, pr) do { \
-                    if ((ch_) < n_chunks) { \
-                        const int j0 = (ch_) * JC, j1 = min(L, j0 + JC); \
-                        float4 *buf = stage + (g & 1u) * buf_f4; \
-                        g++; \
-                        const int n4 = (j1 - j0) * row4; \
-                        GS_FOR_P(GS_STORE_P, pr) \
-                        GS_FETCH((ch_) + GS_DEPTH, pr); \
-                        __syncthreads(); \
-                        int j = j0; \
-                        while (j < j1) { \
-                            const uint32_t word = xw[(j >> 2) * TILE + tid]; \
-                            if ((j & 3) == 0 && j + 4 <= j1) { \
-                                const float4 *r0 = buf + ((j - j0) * q + (word & 0xff)) * NVP; \
-                                const float4 *r1 = buf + ((j + 1 - j0) * q + ((word >> 8) & 0xff)) * NVP; \
-                                const float4 *r2 = buf + ((j + 2 - j0) * q + ((word >> 16) & 0xff)) * NVP; \
-                                const float4 *r3 = buf + ((j + 3 - j0) * q + (word >> 24)) * NVP; \
-                                float4 w0[NV], w1[NV], w2[NV], w3[NV]; \
-_Pragma("unroll") \
-                                for (int v = 0; v < NV; v++) { w0[v] = r0[v]; w1[v] = r1[v]; w2[v] = r2[v]; w3[v] = r3[v]; } \
-_Pragma("unroll") \
-                                for (int v = 0; v < NV; v++) { \
-                                    U[v].x += w0[v].x; U[v].y += w0[v].y; U[v].z += w0[v].z; U[v].w += w0[v].w; \
-                                    U[v].x += w1[v].x; U[v].y += w1[v].y; U[v].z += w1[v].z; U[v].w += w1[v].w; \
-                                    U[v].x += w2[v].x; U[v].y += w2[v].y; U[v].z += w2[v].z; U[v].w += w2[v].w; \
-                                    U[v].x += w3[v].x; U[v].y += w3[v].y; U[v].z += w3[v].z; U[v].w += w3[v].w; \
-                                } \
-                                j += 4; \
-                            } else { \
-                                if (j != i) { \
-                                    const int x = (word >> (8 * (j & 3))) & 0xff; \
-                                    const float4 *row = buf + ((j - j0) * q + x) * NVP; \
-_Pragma("unroll") \
-                                    for (int v = 0; v < NV; v++) { \
-                                        const float4 w = row[v]; \
-                                        U[v].x += w.x; U[v].y += w.y; U[v].z += w.z; U[v].w += w.w; \
-                                    } \
-                                } \
-                                j++; \
-                            } \
-                        } \
-                    } \
-    } while (0)
 
 // Chain states of the tile live in LDS as xs[L/4][TILE][4] bytes: a lane reads four consecutive sites of its chain with
 // one ds_read_b32, and the 64 lanes of a wave read 256 consecutive bytes.  A chunk of JC blocks W[i][j0 .. j0+JC) is
@@ -261,33 +136,6 @@ __global__ __launch_bounds__(TILE) void k_gibbs(const float4 *__restrict__ W, in
         const int c = k / L, j = k - c * L;
         dst[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
     }
-}
-
-// The same draw with one lane per state (groups of QP lanes, QP a power of two >= q): the maximum by a butterfly, the
-// running sum by every lane of the group in state order -- the same additions in the same order as draw_state, so the
-// two forms of the sweep give the same states bit for bit.
-template <int QP>
-__device__ __forceinline__ int draw_group(float U, int a, int q, uint32_t allowed, float beta, uint32_t word0) {
-    const bool on = a < q && ((allowed >> a) & 1u);
-    const float bu = __fmul_rn(beta, U);
-    float m = on ? bu : -INFINITY;
-#pragma unroll
-    for (int o = QP / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const float e = on ? expf(__fsub_rn(bu, m)) : 0.f;
-    const int base = (threadIdx.x & 63) & ~(QP - 1);
-    float S = 0.f;
-    for (int b = 0; b < q; b++) S += __shfl(e, base + b, 64);
-    const float u = uniform24(word0);
-    const float t = __fmul_rn(u, S);
-    int pick = -1, last = 0;
-    S = 0.f;
-    for (int b = 0; b < q; b++) {
-        S += __shfl(e, base + b, 64);
-        const bool okb = (allowed >> b) & 1u;
-        if (okb) last = b;
-        if (okb && pick < 0 && S > t) pick = b;
-    }
-    return pick < 0 ? last : pick;
 }
 
 // The other form of the sweep: lanes = (chain, state), 256 / QP chains per workgroup, the row W[i][j][x_cj][.] read

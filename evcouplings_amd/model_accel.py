@@ -16,6 +16,8 @@ for a block-wise one -- host-side format code, same attributes; measured to be n
 DESIGN_NEXT_ROWS.md section 9.6); the reference has no sampler, so `install()` has nothing to rebind for it.
 `refine_model(model)` refines a model's fields and couplings towards its own `f_i`, `f_ij` with the library's
 Boltzmann-machine loop (`plm_bm_fit`, section 9.7), so that its samples reproduce those frequencies.
+`log_partition(model)` estimates log Z by annealed importance sampling (`plm_ais`, section 9.8), and
+`log_probabilities(model, sequences, log_z)` turns statistical energies into log-probabilities with it.
 """
 from copy import deepcopy
 
@@ -114,6 +116,51 @@ def sample_sequences(model, n_chains, burn_in=100, n_snapshots=1, thin=1, beta=1
     out = out.reshape(-1, L)
     res = letters[out] if as_letters else out
     return (res, en.reshape(-1, 3)) if energies else res
+
+
+def _letters_and_code(model, q):
+    letters = np.array(list(model.alphabet) if isinstance(model.alphabet, str) else model.alphabet).astype("U1")
+    if len(letters) != q:
+        raise ValueError("the model's alphabet has %d letters, its fields %d states" % (len(letters), q))
+    return letters, {a: k for k, a in enumerate(letters)}
+
+
+def log_partition(model, **kw):
+    """
+    log Z of a `CouplingsModel` (anything with `J_ij` [L, L, q, q], `h_i` [L, q] and `alphabet`) by annealed importance
+    sampling (`plm.log_partition`, DESIGN_NEXT_ROWS.md section 9.8; the keyword arguments are its own).  Returns its dict,
+    with `sequences`: the final states of the chains as letters of the model's alphabet.
+    """
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    letters, _ = _letters_and_code(model, q)
+    res = plm.log_partition(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, **kw)
+    res["sequences"] = letters[np.asarray(res["states"]).astype(np.int64)]
+    return res
+
+
+def log_probabilities(model, sequences, log_z):
+    """
+    log P(x) = H(x) - log_z of sequences under a `CouplingsModel`, log_z from `log_partition`.  sequences: an (N, L)
+    matrix of letters of the model's alphabet or of integer states, or a list of strings.
+    """
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    _, code = _letters_and_code(model, q)
+    if len(sequences) and isinstance(sequences[0], str):
+        sequences = [list(s) for s in sequences]
+    mat = np.asarray(sequences)
+    if mat.dtype.kind not in "iu":
+        try:
+            mat = np.vectorize(code.__getitem__, otypes=[np.int8])(mat.astype("U1"))
+        except KeyError as e:
+            raise ValueError("letter %s is not in the model's alphabet" % e)
+    if mat.ndim != 2 or mat.shape[1] != L:
+        raise ValueError("sequences must have the model's %d positions" % L)
+    if mat.min(initial=0) < 0 or mat.max(initial=0) >= q:
+        raise ValueError("states outside 0..%d" % (q - 1))
+    return hamiltonians(mat, np.asarray(model.J_ij), h_i)[:, 0] - float(log_z)
 
 
 def refine_model(model, n_chains=4096, n_epochs=120, sweeps_per_epoch=2, lr=0.5, lr_decay_after=None, lambda_h=None,

@@ -219,6 +219,68 @@ def sample_plan(L, q, n_chains, n_cu=0):
 BM_STATUS = {_lib.STATUS_CONVERGED: "converged", _lib.STATUS_MAXITER: "maxiter", _lib.STATUS_INTERRUPTED: "interrupted"}
 
 
+def log_partition(hi, jij, q, n_chains=4096, n_temps=1000, sweeps_per_temp=1, betas=None, seed=0, steps_per_launch=0,
+                  callback=None, device=0):
+    """
+    log Z of the Potts model (hi, jij) by annealed importance sampling on the GPU (plm_ais, DESIGN_NEXT_ROWS.md section
+    9.8): n_chains chains are annealed from the independent-site model of the fields (log Z_0 in closed form) to the full
+    model over n_temps steps of sweeps_per_temp Gibbs sweeps each, with the inverse temperature beta_k on the couplings
+    only.  betas: None (beta_k = k / n_temps) or the n_temps + 1 values 0 = beta_0 <= ... <= beta_K, which then set
+    n_temps; the result is log Z of the model with the couplings scaled by beta_K.  The steps run in launches of at most
+    steps_per_launch steps (0: about a second each; the result does not depend on it); callback(steps_done, n_steps) is
+    called between launches and stops the anneal by returning a true value.
+    Returns a dict: log_z, log_z0, log_z_se (standard error of log_z from the spread of the weights), ess (effective
+    sample size of the chains), log_w [C], e_j [C] (the tracked coupling energy of the final states), states int8 [C, L],
+    steps_done, status ("converged" or "interrupted": log_z is NaN then).  When beta_K = 1 also mean_energy = sum_c w_c
+    H(x_c) over the normalised weights, H from `hamiltonians` on the final states, and entropy = log_z - mean_energy.
+    """
+    q, C_ = int(q), int(n_chains)
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
+        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
+    L = hi.shape[0]
+    jij = np.ascontiguousarray(jij, dtype=np.float32)
+    if jij.size != L * (L - 1) // 2 * q * q:
+        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    if betas is not None:
+        betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
+        if betas.size < 2:
+            raise ValueError("betas must hold at least beta_0 and beta_1")
+        K = betas.size - 1
+    else:
+        K = int(n_temps)
+    lib = _lib.load()
+    opts = _lib.PlmAisOpts(C_, K, int(sweeps_per_temp), int(steps_per_launch), _ptr(betas), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    n_out = max(C_, 1)
+    log_w, e_j, states = np.zeros(n_out), np.zeros(n_out), np.zeros((n_out, L), np.int8)
+    res = _lib.PlmAisResult(0.0, 0.0, 0.0, 0.0, _ptr(log_w), _ptr(e_j), _ptr(states), 0, 0)
+    failure = []
+
+    def _cb(done, total, _user):
+        try:
+            return 1 if callback(int(done), int(total)) else 0
+        except BaseException as exc:     # an exception must not cross the C frames
+            failure.append(exc)
+            return 1
+
+    cb = _lib.AIS_CB(_cb) if callback is not None else _lib.AIS_CB()
+    check(lib.plm_ais(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb, None, C.byref(res)))
+    if failure:
+        raise failure[0]
+    out = dict(log_z=float(res.log_z), log_z0=float(res.log_z0), log_z_se=float(res.log_z_se), ess=float(res.ess),
+               log_w=log_w, e_j=e_j, states=states, steps_done=int(res.steps_done), status=BM_STATUS[int(res.status)])
+    last = 1.0 if betas is None else float(betas[-1])
+    if res.status == _lib.STATUS_CONVERGED and last == 1.0:
+        if L > 1:
+            H = hamiltonians(states, q, hi, jij, device=device)[:, 0]
+        else:
+            H = hi[0].astype(np.float64)[states[:, 0]]
+        w = np.exp(log_w - log_w.max())
+        out["mean_energy"] = float((w / w.sum()) @ H)
+        out["entropy"] = out["log_z"] - out["mean_energy"]
+    return out
+
+
 def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, lr_decay_after=0, lambda_h=0.0,
            lambda_j=0.0, tol=0.0, seed=0, start=None, first_epoch=0, callback=None, device=0):
     """

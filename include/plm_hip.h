@@ -377,6 +377,46 @@ typedef int (*plm_bm_epoch_cb)(int32_t epoch, double max_dfi, double max_dfij, d
 int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *fij, const float *x_start,
                const plm_bm_opts *opts, int device, void *stream, plm_bm_epoch_cb cb, void *user, plm_bm_result *result);
 
+/* ---- log Z by annealed importance sampling (DESIGN_NEXT_ROWS.md section 9.8) ---------------------------------------
+ * Estimates the partition function of the model (h, J) of plm_sample along the path
+ *   p_beta(x) ~ exp(sum_i h_i(x_i) + beta sum_{i<j} J_ij(x_i, x_j)),
+ * from the independent-site model of the fields (beta = 0: sampled exactly, log Z_0 = sum_i log sum_a exp h_i(a)) to the
+ * couplings scaled by the last beta.  Schedule: K + 1 float32 values beta_0 = 0 <= beta_1 <= ... <= beta_K, all finite;
+ * betas == NULL: beta_k = (float)((double)k / K).  beta_K need not be 1: the result is log Z of the model with the
+ * couplings scaled by beta_K, so every prefix of a schedule is a schedule.
+ * Chain c starts from plm_sample's start rule at beta = 1 with all states allowed.  E = 1/2 sum_i (double)U_i[x_i] there,
+ * U_i[a] = sum_{j != i} J_ij(a, x_j) in float32 from 0 over j = 0 .. L-1.  Step k = 1 .. K: log w += ((double)beta_k -
+ * (double)beta_{k-1}) E, then sweeps_per_temp = n sweeps with the indices (k-1) n .. k n - 1; a site update draws (the draw
+ * and the Philox counter of plm_sample) on fadd(h_i(a), fmul(beta_k, U_i[a])) and adds (double)U_i[a_new] -
+ * (double)U_i[a_old] to E in float64.
+ *   log_z = log_z0 + m + log((1/C) sum_c exp(log_w[c] - m)), m = max log_w, summed in chain order in float64
+ *   ess = (sum w)^2 / sum w^2, log_z_se = std(w, ddof = 1) / (sqrt(C) mean w) with w = exp(log_w - m); 0 for C = 1
+ * log_w[c] depends on (seed, c, model, schedule, n) only: not on C, the launch plan or steps_per_launch.  The steps run in
+ * launches of at most steps_per_launch steps (0: about a second each); cb, if given, is called between launches and
+ * cancels by returning non-zero: status PLM_STATUS_INTERRUPTED, log_z, log_z_se and ess NaN, the arrays hold the state
+ * reached after steps_done steps.  PLM_EINVAL (before the device is looked at): NULL opts or result, sizes below 1, a
+ * schedule that does not start at 0, decreases or holds a non-finite value, K n >= 2^32 - 1; PLM_EUNSUPPORTED: q outside
+ * 2..32; PLM_ENOMEM before any array is read. */
+typedef struct {
+    int32_t n_chains;          /* C >= 1                                                               */
+    int32_t n_temps;           /* K >= 1 annealing steps                                               */
+    int32_t sweeps_per_temp;   /* n >= 1                                                               */
+    int32_t steps_per_launch;  /* 0 = default; any value gives the same bits                           */
+    const float *betas;        /* NULL, or K + 1 values as defined above                               */
+    uint64_t seed;
+} plm_ais_opts;
+typedef struct {
+    double log_z, log_z0, log_z_se, ess;
+    double *log_w;             /* [C] or NULL                                                          */
+    double *e_j;               /* [C] tracked coupling energy of the final states, or NULL             */
+    int8_t *states;            /* C x L final states, or NULL                                          */
+    int32_t steps_done;
+    int32_t status;            /* PLM_STATUS_CONVERGED when all K steps ran, else PLM_STATUS_INTERRUPTED */
+} plm_ais_result;
+typedef int (*plm_ais_cb)(int32_t steps_done, int32_t n_steps, void *user);
+int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_ais_opts *opts, int device,
+            void *stream, plm_ais_cb cb, void *user, plm_ais_result *result);
+
 /* ---- mean-field direct coupling analysis ---------------------------
  * Replaces the arithmetic of evcouplings/couplings/mean_field.py:163-222 (MeanFieldDCA.fit: weights,
  * frequencies, pseudo-count regularisation :717-790, covariance matrix :897-940, J = -C^-1 :204-210 and
