@@ -8,7 +8,6 @@
 //                  after the loop, and E followed through U[a_new] - U[a_old], which the lane holds when it draws
 //   k_ais_direct   the direct form: lanes = (chain, state), the two U by shuffles inside the group
 // A launch runs the steps [k0, k1) of the schedule; the first one draws the start states and measures E there.
-#include "../../include/plm_hip.h"
 #include "plm_sample_internal.h"
 #include "plm_gibbs_device.h"
 #include <hip/hip_runtime.h>
@@ -16,9 +15,6 @@
 #include <stdint.h>
 #include <algorithm>
 #include <vector>
-
-int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
-int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
 
 namespace {
 
@@ -252,57 +248,22 @@ struct AisArgs {
     double *e, *logw;
 };
 
-template <int NV, int TILE>
-hipError_t launch_tiled_t(const gibbs::SweepPlan &p, hipStream_t st, const AisArgs &a) {
-    auto kern = k_ais<NV, TILE>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.C + TILE - 1) / TILE)), dim3(TILE), p.lds, st, a.W, a.L, a.q, a.C, p.JC,
-                       a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed, (uint32_t)(a.seed & 0xFFFFFFFFu),
-                       (uint32_t)(a.seed >> 32), a.states, a.e, a.logw);
-    return hipGetLastError();
-}
-
-template <int NV>
-hipError_t launch_tiled_nv(const gibbs::SweepPlan &p, hipStream_t st, const AisArgs &a) {
-    switch (p.tile) {
-    case 256: return launch_tiled_t<NV, 256>(p, st, a);
-    case 128: return launch_tiled_t<NV, 128>(p, st, a);
-    default: return launch_tiled_t<NV, 64>(p, st, a);
-    }
-}
-
-template <int QP>
-hipError_t launch_direct_t(const gibbs::SweepPlan &p, hipStream_t st, const AisArgs &a) {
-    auto kern = k_ais_direct<QP>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-    if (e != hipSuccess) return e;
-    constexpr int CPW = 256 / QP;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.C + CPW - 1) / CPW)), dim3(256), p.lds, st, (const float *)a.W, a.L, a.q,
-                       (a.q + 3) / 4 * 4, a.C, a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed,
-                       (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), a.states, a.e, a.logw);
-    return hipGetLastError();
-}
-
-// the steps [k0, k1) under the plan gibbs::plan_sweeps made (for the direct form plan.tile = 256 / group size)
+// the steps [k0, k1) under the plan gibbs::plan_sweeps made
 hipError_t launch_steps(const gibbs::SweepPlan &p, hipStream_t st, const AisArgs &a) {
-    if (p.direct) {
-        switch (256 / p.tile) {
-        case 2: return launch_direct_t<2>(p, st, a);
-        case 4: return launch_direct_t<4>(p, st, a);
-        case 8: return launch_direct_t<8>(p, st, a);
-        case 16: return launch_direct_t<16>(p, st, a);
-        case 32: return launch_direct_t<32>(p, st, a);
-        }
-        return hipErrorInvalidValue;
-    }
-#define AIS_CASE(n) \
-    case n: return launch_tiled_nv<n>(p, st, a);
-    switch (p.NV) {
-        AIS_CASE(1) AIS_CASE(2) AIS_CASE(3) AIS_CASE(4) AIS_CASE(5) AIS_CASE(6) AIS_CASE(7) AIS_CASE(8)
-    }
-#undef AIS_CASE
-    return hipErrorInvalidValue;
+    const uint32_t seed_lo = (uint32_t)(a.seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(a.seed >> 32);
+    return gibbs::dispatch(
+        p,
+        [&](auto nv, auto tile) {
+            return gibbs::launch(k_ais<nv(), tile()>, (unsigned)((a.C + tile() - 1) / tile()), tile(), p, st, a.W, a.L, a.q,
+                                 a.C, p.JC, a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed, seed_lo, seed_hi, a.states, a.e,
+                                 a.logw);
+        },
+        [&](auto qp) {
+            const int cpw = 256 / qp();              // chains per workgroup
+            return gibbs::launch(k_ais_direct<qp()>, (unsigned)((a.C + cpw - 1) / cpw), 256, p, st, (const float *)a.W, a.L,
+                                 a.q, p.NV * 4, a.C, a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed, seed_lo, seed_hi,
+                                 a.states, a.e, a.logw);
+        });
 }
 
 // Steps per launch that keep a launch near a second: a workgroup of the tiled form spends about 150 ns per pair of sites
@@ -325,7 +286,7 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
     if (L < 1 || C < 1 || K < 1 || n < 1 || opts->steps_per_launch < 0)
         return plm_fail(PLM_EINVAL, "need n_sites >= 1, n_chains >= 1, n_temps >= 1, sweeps_per_temp >= 1, "
                                     "steps_per_launch >= 0 (got %d, %d, %d, %d, %d)", L, C, K, n, opts->steps_per_launch);
-    if (q < 2 || q > GS_Q) return plm_fail(PLM_EUNSUPPORTED, "annealed importance sampling supports 2..32 states (got %d)", q);
+    PLM_TRY(gibbs::check_states(q, "annealed importance sampling"));
     if ((double)K * (double)n >= 4294967295.0)
         return plm_fail(PLM_EINVAL, "n_temps x sweeps_per_temp must stay below 2^32 - 1 sweeps");
     if (opts->betas) {
@@ -335,27 +296,17 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
                 return plm_fail(PLM_EINVAL, "betas must be finite and non-decreasing (betas[%d] = %g after %g)", k,
                                 (double)opts->betas[k], (double)opts->betas[k - 1]);
     }
-    int rc = plm_check_device(device);
-    if (rc) return rc;
+    PLM_TRY(plm_check_device(device));
     // sizes first: nothing below this point is dereferenced before the device is known to hold the call
-    const int QS = (q + 3) / 4 * 4;
-    const double table_b = 4.0 * ((double)L * L * q * QS + (double)L * QS);
-    const double canon_b = 4.0 * ((double)L * q + (double)L * (L - 1) / 2 * q * q);
+    const double table_b = gibbs::table_bytes(L, q);
     const double chain_b = (double)C * L + 16.0 * C + 4.0 * ((double)K + 1.0);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipMemGetInfo failed");
-    if (table_b + canon_b + chain_b > (double)free_b)
-        return plm_fail(PLM_ENOMEM, "annealed importance sampling needs %.2f GB of device memory (%.2f GB of it the "
-                                    "expanded couplings), %.2f GB are free (of %.1f GB)",
-                        (table_b + canon_b + chain_b) / 1e9, table_b / 1e9, free_b / 1e9, total_b / 1e9);
-    if ((double)C * L >= 2147483647.0) return plm_fail(PLM_EINVAL, "n_chains x n_sites must stay below 2^31");
+    PLM_TRY(plm_check_free(table_b + gibbs::canon_bytes(L, q) + chain_b, "annealed importance sampling", table_b));
+    PLM_TRY(gibbs::check_chain_sites(C, L));
     if (!x_canonical) return plm_fail(PLM_EINVAL, "NULL model");
     gibbs::SweepPlan plan;
-    rc = gibbs::plan_sweeps(L, q, C, device, &plan);
-    if (rc) return rc;
+    PLM_TRY(gibbs::plan_sweeps(L, q, C, device, &plan));
     int n_cu = 0;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
-        return plm_fail(PLM_EDEVICE, "hipDeviceGetAttribute failed");
+    PLM_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
     const int per_launch = opts->steps_per_launch > 0 ? std::min(opts->steps_per_launch, K)
                                                       : default_steps_per_launch(plan, L, C, n, K, n_cu);
 
@@ -372,47 +323,32 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
     for (int k = 0; k <= K; k++) betas[k] = opts->betas ? opts->betas[k] : (float)((double)k / (double)K);
 
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_canon = (size_t)L * q + (size_t)L * (L - 1) / 2 * q * q;
-    const size_t CL = (size_t)C * L;
+    const size_t n_canon = (size_t)plm_n_canon(L, q), CL = (size_t)C * L;
     float *canon = nullptr, *d_betas = nullptr;
     float4 *W = nullptr;
     int8_t *states = nullptr;
     double *d_e = nullptr, *d_logw = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {canon, d_betas, W, states, d_e, d_logw};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-#define AIS_ALLOC(ptr, bytes)                                                                  \
-    if (hipMalloc((void **)&ptr, std::max<size_t>((bytes), 16)) != hipSuccess) {               \
-        ptr = nullptr;                                                                         \
-        return done(plm_fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed", (size_t)(bytes)));   \
-    }
-    AIS_ALLOC(canon, n_canon * sizeof(float));
-    AIS_ALLOC(d_betas, betas.size() * sizeof(float));
-    AIS_ALLOC(W, gibbs::table_float4(L, q) * sizeof(float4));
-    AIS_ALLOC(states, CL);
-    AIS_ALLOC(d_e, (size_t)C * sizeof(double));
-    AIS_ALLOC(d_logw, (size_t)C * sizeof(double));
-#undef AIS_ALLOC
-    hipError_t e;
-#define ET(expr)              \
-    if ((e = (expr)) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));
-    ET(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
-    ET(hipMemcpyAsync(d_betas, betas.data(), betas.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    ET(gibbs::expand(st, canon, L, q, W));
-    AisArgs args = {W, L, q, C, d_betas, 0, 0, n, 1, q == 32 ? 0xFFFFFFFFu : ((1u << q) - 1u), opts->seed, states, d_e,
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&canon, n_canon));
+    PLM_TRY(mem.alloc(&d_betas, betas.size()));
+    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(mem.alloc(&states, CL));
+    PLM_TRY(mem.alloc(&d_e, (size_t)C));
+    PLM_TRY(mem.alloc(&d_logw, (size_t)C));
+    PLM_HIP(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemcpyAsync(d_betas, betas.data(), betas.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(gibbs::expand(st, canon, L, q, W));
+    AisArgs args = {W, L, q, C, d_betas, 0, 0, n, 1, plm_state_mask(q), opts->seed, states, d_e,
                     d_logw};
     int steps_done = 0, status = PLM_STATUS_CONVERGED;
     while (steps_done < K) {
         args.k0 = steps_done;
         args.k1 = std::min(K, steps_done + per_launch);
         args.first = steps_done == 0;
-        ET(launch_steps(plan, st, args));
+        PLM_HIP(launch_steps(plan, st, args));
         steps_done = args.k1;
         if (cb && steps_done < K) {
-            ET(hipStreamSynchronize(st));
+            PLM_HIP(hipStreamSynchronize(st));
             if (cb((int32_t)steps_done, (int32_t)K, user)) {
                 status = PLM_STATUS_INTERRUPTED;
                 break;
@@ -420,18 +356,17 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
         }
     }
     std::vector<double> logw((size_t)C);
-    ET(hipMemcpyAsync(logw.data(), d_logw, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (result->e_j) ET(hipMemcpyAsync(result->e_j, d_e, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (result->states) ET(hipMemcpyAsync(result->states, states, CL, hipMemcpyDeviceToHost, st));
-    ET(hipStreamSynchronize(st));
-#undef ET
+    PLM_HIP(hipMemcpyAsync(logw.data(), d_logw, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (result->e_j) PLM_HIP(hipMemcpyAsync(result->e_j, d_e, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (result->states) PLM_HIP(hipMemcpyAsync(result->states, states, CL, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
     if (result->log_w) std::copy(logw.begin(), logw.end(), result->log_w);
     result->log_z0 = log_z0;
     result->steps_done = steps_done;
     result->status = status;
     if (status == PLM_STATUS_INTERRUPTED) {
         result->log_z = result->log_z_se = result->ess = NAN;
-        return done(PLM_OK);
+        return PLM_OK;
     }
     // log Z = log Z_0 + log mean w, the sums in chain order in float64
     double m = logw[0], s1 = 0.0, s2 = 0.0;
@@ -450,5 +385,5 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
         var += d * d;
     }
     result->log_z_se = C > 1 ? sqrt(var / (C - 1)) / (sqrt((double)C) * mean) : 0.0;
-    return done(PLM_OK);
+    return PLM_OK;
 }

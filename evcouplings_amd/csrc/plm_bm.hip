@@ -9,15 +9,11 @@
 //   k_bm_stats      p = n / C, and per workgroup max |fi - pi|, max |fij - pij|, sum (fij - pij)^2
 //   k_bm_trace      the trace row from the partials, in a fixed order
 //   k_bm_update     x <- x + lr ((f - p) - 2 lambda x)
-#include "../../include/plm_hip.h"
 #include "plm_sample_internal.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <algorithm>
-
-int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
-int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
 
 namespace {
 
@@ -187,44 +183,32 @@ int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *
     if (L < 1 || C < 1 || E < 1 || K < 1 || e0 < 0 || T < 0)
         return plm_fail(PLM_EINVAL, "need n_sites >= 1, n_chains >= 1, n_epochs >= 1, sweeps_per_epoch >= 1, first_epoch >= 0, "
                                     "lr_decay_after >= 0 (got %d, %d, %d, %d, %d, %d)", L, C, E, K, e0, T);
-    if (q < 2 || q > 32) return plm_fail(PLM_EUNSUPPORTED, "the sampler supports 2..32 states (got %d)", q);
+    PLM_TRY(gibbs::check_states(q, "the sampler"));
     if (bad(opts->lr)) return plm_fail(PLM_EINVAL, "lr must be finite and >= 0 (got %g)", (double)opts->lr);
     if (bad(opts->lambda_h)) return plm_fail(PLM_EINVAL, "lambda_h must be finite and >= 0 (got %g)", (double)opts->lambda_h);
     if (bad(opts->lambda_j)) return plm_fail(PLM_EINVAL, "lambda_j must be finite and >= 0 (got %g)", (double)opts->lambda_j);
     if (bad(opts->tol)) return plm_fail(PLM_EINVAL, "tol must be finite and >= 0 (got %g)", (double)opts->tol);
     if (((double)e0 + (double)E) * (double)K >= 4294967295.0)
         return plm_fail(PLM_EINVAL, "(first_epoch + n_epochs) sweeps_per_epoch must stay below 2^32 - 1 sweeps");
-    int rc = plm_check_device(device);
-    if (rc) return rc;
+    PLM_TRY(plm_check_device(device));
     // sizes first: nothing below this point is dereferenced before the device is known to hold the call
-    const int QS = (q + 3) / 4 * 4;
-    const double n_canon_d = (double)L * q + (double)L * (L - 1) / 2 * q * q;
-    const double table_b = 4.0 * ((double)L * L * q * QS + (double)L * QS);
-    const double canon_b = 4.0 * 4.0 * n_canon_d;                               // x, f, p and the counts
+    const double table_b = gibbs::table_bytes(L, q);
+    const double canon_b = 4.0 * gibbs::canon_bytes(L, q);                      // x, f, p and the counts
     const double state_b = 3.0 * ((double)C + 3.0) * L;                         // two chain buffers and the site-major copy
     const double small_b = 32.0 * E + 24.0 * BM_STAT_BLOCKS;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipMemGetInfo failed");
-    if (table_b + canon_b + state_b + small_b > (double)free_b)
-        return plm_fail(PLM_ENOMEM, "the refinement needs %.2f GB of device memory (%.2f GB of it the expanded couplings), "
-                                    "%.2f GB are free (of %.1f GB)", (table_b + canon_b + state_b + small_b) / 1e9,
-                        table_b / 1e9, free_b / 1e9, total_b / 1e9);
-    if ((double)C * L >= 2147483647.0) return plm_fail(PLM_EINVAL, "n_chains x n_sites must stay below 2^31");
+    PLM_TRY(plm_check_free(table_b + canon_b + state_b + small_b, "the refinement", table_b));
+    PLM_TRY(gibbs::check_chain_sites(C, L));
     if (!fi) return plm_fail(PLM_EINVAL, "NULL fi");
     if (!fij && L > 1) return plm_fail(PLM_EINVAL, "NULL fij");
     if (!x_start) return plm_fail(PLM_EINVAL, "NULL x_start");
     const size_t CL = (size_t)C * L;
-    if (opts->start)
-        for (size_t k = 0; k < CL; k++) {
-            const int v = opts->start[k];
-            if (v < 0 || v >= q) return plm_fail(PLM_EINVAL, "start[%zu] = %d outside 0..%d", k, v, q - 1);
-        }
+    const uint32_t allowed = plm_state_mask(q);
+    if (opts->start) PLM_TRY(gibbs::check_start(opts->start, C, L, q, allowed, nullptr));
     gibbs::SweepPlan plan;
-    rc = gibbs::plan_sweeps(L, q, C, device, &plan);
-    if (rc) return rc;
+    PLM_TRY(gibbs::plan_sweeps(L, q, C, device, &plan));
 
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_h = (size_t)L * q, n_j = (size_t)L * (L - 1) / 2 * q * q, n = n_h + n_j;
+    const size_t n_h = (size_t)L * q, n = (size_t)plm_n_canon(L, q), n_j = n - n_h;
     const int Cp = (C + 3) / 4 * 4, n4 = Cp / 4;
     const int JB = q <= 22 ? 16 : 8;                                            // at most 32 KB of histograms
     const int n_jb = (L + JB - 1) / JB;
@@ -233,7 +217,6 @@ int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *
     const int n_z = (int)std::min<long>(std::max<long>(1, (1024 + useful - 1) / useful), std::max(1, (n4 + 255) / 256));
     const int per_z = (n4 + n_z - 1) / n_z;
     const int n_stat = (int)std::min<size_t>(BM_STAT_BLOCKS, (n + 255) / 256);
-    const uint32_t allowed = q == 32 ? 0xFFFFFFFFu : ((1u << q) - 1u);
 
     float *x = nullptr, *f = nullptr, *p = nullptr;
     float4 *W = nullptr;
@@ -241,40 +224,22 @@ int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *
     int8_t *ch[2] = {nullptr, nullptr};
     uint8_t *xT = nullptr;
     double *part = nullptr, *trace = nullptr, *row_host = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {x, f, p, W, cnt, ch[0], ch[1], xT, part, trace};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        if (row_host) (void)hipHostFree(row_host);
-        return code;
-    };
-#define BM_ALLOC(ptr, bytes)                                                                   \
-    if (hipMalloc((void **)&ptr, std::max<size_t>((bytes), 16)) != hipSuccess) {               \
-        ptr = nullptr;                                                                         \
-        return done(plm_fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed", (size_t)(bytes)));   \
-    }
-    BM_ALLOC(x, n * sizeof(float));
-    BM_ALLOC(f, n * sizeof(float));
-    BM_ALLOC(p, n * sizeof(float));
-    BM_ALLOC(W, gibbs::table_float4(L, q) * sizeof(float4));
-    BM_ALLOC(cnt, n * sizeof(int32_t));
-    BM_ALLOC(ch[0], CL);
-    BM_ALLOC(ch[1], CL);
-    BM_ALLOC(xT, (size_t)L * Cp);
-    BM_ALLOC(part, (size_t)3 * BM_STAT_BLOCKS * sizeof(double));
-    BM_ALLOC(trace, (size_t)4 * E * sizeof(double));
-#undef BM_ALLOC
-    if (hipHostMalloc((void **)&row_host, 4 * sizeof(double)) != hipSuccess) {
-        row_host = nullptr;
-        return done(plm_fail(PLM_ENOMEM, "hipHostMalloc of the trace row failed"));
-    }
-    hipError_t e;
-#define ET(expr)              \
-    if ((e = (expr)) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));
-    ET(hipMemcpyAsync(x, x_start, n * sizeof(float), hipMemcpyHostToDevice, st));
-    ET(hipMemcpyAsync(f, fi, n_h * sizeof(float), hipMemcpyHostToDevice, st));
-    if (n_j) ET(hipMemcpyAsync(f + n_h, fij, n_j * sizeof(float), hipMemcpyHostToDevice, st));
-    if (opts->start) ET(hipMemcpyAsync(ch[0], opts->start, CL, hipMemcpyHostToDevice, st));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&x, n));
+    PLM_TRY(mem.alloc(&f, n));
+    PLM_TRY(mem.alloc(&p, n));
+    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(mem.alloc(&cnt, n));
+    PLM_TRY(mem.alloc(&ch[0], CL));
+    PLM_TRY(mem.alloc(&ch[1], CL));
+    PLM_TRY(mem.alloc(&xT, (size_t)L * Cp));
+    PLM_TRY(mem.alloc(&part, (size_t)3 * BM_STAT_BLOCKS));
+    PLM_TRY(mem.alloc(&trace, (size_t)4 * E));
+    PLM_TRY(mem.alloc_pinned(&row_host, 4));
+    PLM_HIP(hipMemcpyAsync(x, x_start, n * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemcpyAsync(f, fi, n_h * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n_j) PLM_HIP(hipMemcpyAsync(f + n_h, fij, n_j * sizeof(float), hipMemcpyHostToDevice, st));
+    if (opts->start) PLM_HIP(hipMemcpyAsync(ch[0], opts->start, CL, hipMemcpyHostToDevice, st));
 
     const bool host_decides = cb != nullptr || opts->tol > 0.f;
     int cur = 0;                                   // ch[cur]: the states the next sweeps start from
@@ -283,28 +248,28 @@ int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *
         const int64_t g = (int64_t)e0 + ep;
         float lr_g = opts->lr;
         if (T > 0 && g + 1 > T) lr_g = (float)((double)opts->lr * (double)T / (double)(g + 1));
-        ET(gibbs::expand(st, x, L, q, W));
+        PLM_HIP(gibbs::expand(st, x, L, q, W));
         const int8_t *src = (ep == 0 && !opts->start) ? nullptr : ch[cur];
-        ET(gibbs::sweeps(plan, st, W, L, q, C, src, nullptr, allowed, 1.0f, opts->seed, (uint32_t)(g * K), K, ch[cur ^ 1]));
+        PLM_HIP(gibbs::sweeps(plan, st, W, L, q, C, src, nullptr, allowed, 1.0f, opts->seed, (uint32_t)(g * K), K, ch[cur ^ 1]));
         cur ^= 1;
         hipLaunchKernelGGL(k_bm_transpose, dim3((unsigned)((Cp + 63) / 64), (unsigned)((L + 63) / 64)), dim3(256), 0, st,
                            ch[cur], C, L, Cp, xT);
-        ET(hipGetLastError());
-        ET(hipMemsetAsync(cnt, 0, n * sizeof(int32_t), st));
+        PLM_HIP(hipGetLastError());
+        PLM_HIP(hipMemsetAsync(cnt, 0, n * sizeof(int32_t), st));
         hipLaunchKernelGGL(k_bm_count, dim3((unsigned)n_jb, (unsigned)L, (unsigned)n_z), dim3(256),
                            (size_t)JB * q * q * sizeof(int32_t), st, (const uint32_t *)xT, L, q, n4, JB, per_z, cnt,
                            cnt + n_h);
-        ET(hipGetLastError());
+        PLM_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_bm_stats, dim3((unsigned)n_stat), dim3(256), 0, st, cnt, f, (int64_t)n, (int64_t)n_h, (float)C,
                            p, part);
-        ET(hipGetLastError());
+        PLM_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_bm_trace, dim3(1), dim3(256), 0, st, part, n_stat, (double)n_j, (double)lr_g,
                            trace + (size_t)4 * ep);
-        ET(hipGetLastError());
+        PLM_HIP(hipGetLastError());
         rows = ep + 1;
         if (host_decides) {
-            ET(hipMemcpyAsync(row_host, trace + (size_t)4 * ep, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-            ET(hipStreamSynchronize(st));
+            PLM_HIP(hipMemcpyAsync(row_host, trace + (size_t)4 * ep, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+            PLM_HIP(hipStreamSynchronize(st));
             if (opts->tol > 0.f && row_host[0] <= (double)opts->tol && row_host[1] <= (double)opts->tol) {
                 status = PLM_STATUS_CONVERGED;
                 break;
@@ -317,18 +282,17 @@ int plm_bm_fit(int32_t n_sites, int32_t n_states, const float *fi, const float *
         if (lr_g != 0.f) {
             hipLaunchKernelGGL(k_bm_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, f, p, (int64_t)n,
                                (int64_t)n_h, lr_g, 2.f * opts->lambda_h, 2.f * opts->lambda_j);
-            ET(hipGetLastError());
+            PLM_HIP(hipGetLastError());
         }
         done_epochs = ep + 1;
     }
-    if (result->x_out) ET(hipMemcpyAsync(result->x_out, x, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (result->pi_out) ET(hipMemcpyAsync(result->pi_out, p, n_h * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (result->pij_out && n_j) ET(hipMemcpyAsync(result->pij_out, p + n_h, n_j * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (result->chains_out) ET(hipMemcpyAsync(result->chains_out, ch[cur], CL, hipMemcpyDeviceToHost, st));
-    if (result->trace) ET(hipMemcpyAsync(result->trace, trace, (size_t)4 * rows * sizeof(double), hipMemcpyDeviceToHost, st));
-    ET(hipStreamSynchronize(st));
-#undef ET
+    if (result->x_out) PLM_HIP(hipMemcpyAsync(result->x_out, x, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (result->pi_out) PLM_HIP(hipMemcpyAsync(result->pi_out, p, n_h * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (result->pij_out && n_j) PLM_HIP(hipMemcpyAsync(result->pij_out, p + n_h, n_j * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (result->chains_out) PLM_HIP(hipMemcpyAsync(result->chains_out, ch[cur], CL, hipMemcpyDeviceToHost, st));
+    if (result->trace) PLM_HIP(hipMemcpyAsync(result->trace, trace, (size_t)4 * rows * sizeof(double), hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
     result->epochs_done = done_epochs;
     result->status = status;
-    return done(PLM_OK);
+    return PLM_OK;
 }

@@ -4,6 +4,7 @@
 // PLM_EDEVICE otherwise.
 #include "../../include/plm_hip.h"
 #include "plm_internal.h"
+#include "plm_host_util.h"
 
 #include <algorithm>
 #include <chrono>
@@ -39,23 +40,7 @@ int plm_fail(int code, const char *fmt, ...) {
     va_end(ap);
     return fail(code, "%s", buf);
 }
-int plm_meanfield_device(const float *fi, const float *fij, int L, int q, double pseudo_count, hipStream_t st,
-                         double *hi, double *jfull, float *jpairs, double *di);   // plm_meanfield.hip
-int plm_direct_information_device(const double *jdense, const double *rfi, int L, int q, hipStream_t st, double *di);
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess)                                                                     \
-            return fail(e__ == hipErrorOutOfMemory ? PLM_ENOMEM : PLM_EDEVICE, "%s failed: %s (%s:%d)", \
-                        #expr, hipGetErrorString(e__), __FILE__, __LINE__);                        \
-    } while (0)
-#define PLM_TRY(expr)                  \
-    do {                               \
-        int rc__ = (expr);             \
-        if (rc__ != PLM_OK) return rc__; \
-    } while (0)
 
 double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -67,10 +52,10 @@ int check_device(int device) {
         return fail(PLM_EDEVICE, "no HIP device visible (libplm_hip has no CPU path)");
     if (device < 0 || device >= n) return fail(PLM_EINVAL, "device %d out of range (%d visible)", device, n);
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    PLM_HIP(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PLM_EDEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-    HIP_TRY(hipSetDevice(device));
+    PLM_HIP(hipSetDevice(device));
     return PLM_OK;
 }
 
@@ -350,6 +335,11 @@ struct plm_ctx {
 
 namespace {
 
+// the padded row-major host image of the d.N sequences that the forward and reweighting kernels read
+std::vector<int8_t> padded_rows(const PlmDims &d, const int8_t *seqs) {
+    return plm_padded_rows(seqs, d.N, d.L, (size_t)d.Np + 32, (size_t)d.Lp32, (int8_t)PLM_PAD_STATE);
+}
+
 // Precision of the next evaluations: plain (f16 forward GEMM, __expf, planes_base digit planes) or accurate (exact forward
 // GEMM, exact softmax arguments, four digit planes).  PLM_BWD_PLANES pins the plane count (measurements).
 void ctx_set_accurate(plm_ctx *c, bool on) {
@@ -362,26 +352,17 @@ void ctx_set_accurate(plm_ctx *c, bool on) {
     c->d.gscale = wmax / (qmax * (float)PLM_BWD_ONEHOT_VALUE);   // the one-hot operand of k_bwd carries -128
 }
 
-template <typename T> int dalloc(T **p, size_t n_elems) {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(n_elems, 1) * sizeof(T));
-    if (e != hipSuccess)
-        return fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed: %s", n_elems * sizeof(T), hipGetErrorString(e));
-    *p = (T *)q;
-    return PLM_OK;
-}
-
 int ctx_alloc_lbfgs(plm_ctx *c, int m) {
     if (c->xp && c->hist_m >= m) return PLM_OK;
     const size_t n = (size_t)c->d.n_local;
     if (!c->xp) {
-        PLM_TRY(dalloc(&c->xp, n));
-        PLM_TRY(dalloc(&c->gp, n));
-        PLM_TRY(dalloc(&c->dir, n));
+        PLM_TRY(plm_dalloc(&c->xp, n));
+        PLM_TRY(plm_dalloc(&c->gp, n));
+        PLM_TRY(plm_dalloc(&c->dir, n));
     }
-    if (c->hist) hipFree(c->hist);
+    if (c->hist) (void)hipFree(c->hist);
     c->hist = nullptr;
-    PLM_TRY(dalloc(&c->hist, n * 2 * (size_t)m));
+    PLM_TRY(plm_dalloc(&c->hist, n * 2 * (size_t)m));
     c->hist_m = m;
     return PLM_OK;
 }
@@ -395,7 +376,7 @@ int ctx_collective(plm_ctx *c, int op, void *send, void *recv, const int64_t *sc
         return PLM_OK;
     }
     if (!c->collective) return fail(PLM_EINVAL, "sharded-state mode needs a collective callback or an RCCL communicator");
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     if (c->collective(op, send, recv, scounts, rcounts, c->d.nshards, c->d.shard, c->collective_user) != 0)
         return fail(PLM_ECALLBACK, "collective callback failed (op %d)", op);
     return PLM_OK;
@@ -412,17 +393,17 @@ int ctx_allreduce_scalars(plm_ctx *c, int first, int count) {
 // group regulariser (lambda_group > 0): squared norms of the coupling blocks of the current x, for k_assemble
 int group_norms(plm_ctx *c) {
     if (!(c->prob.lambda_group > 0)) return PLM_OK;
-    if (!c->pair_n2) PLM_TRY(dalloc(&c->pair_n2, (size_t)std::max<int64_t>(1, c->d.np_own) * 256));
-    HIP_TRY(plm_launch_pair_norms(c->d, c->x, c->pair_n2, c->st));
+    if (!c->pair_n2) PLM_TRY(plm_dalloc(&c->pair_n2, (size_t)std::max<int64_t>(1, c->d.np_own) * 256));
+    PLM_HIP(plm_launch_pair_norms(c->d, c->x, c->pair_n2, c->st));
     return PLM_OK;
 }
 int vp_alloc(plm_ctx *c);
 int forward_at_x(plm_ctx *c) {
     const PlmDims &d = c->d;
     PLM_TRY(vp_alloc(c));
-    HIP_TRY(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, c->fwd_accurate, c->st));
-    HIP_TRY(plm_launch_h64_init(d, c->x, c->h64, c->st));
-    HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr, nullptr, nullptr, PLM_VP_ALWAYS, c->st));
+    PLM_HIP(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, c->fwd_accurate, c->st));
+    PLM_HIP(plm_launch_h64_init(d, c->x, c->h64, c->st));
+    PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr, nullptr, nullptr, PLM_VP_ALWAYS, c->st));
     return PLM_OK;
 }
 
@@ -435,17 +416,17 @@ float *x_rectangles(plm_ctx *c) { return c->x + c->d.nh_pad_l + (size_t)c->d.ntr
 int ctx_eval_enqueue_sharded(plm_ctx *c) {
     const PlmDims &d = c->d;
     PLM_TRY(ctx_collective(c, PLM_COLL_ALLTOALL, x_rectangles(c), c->xhalo, c->x_send.data(), c->x_recv.data()));
-    HIP_TRY(plm_launch_maxabs2(c->x + d.nh_pad_l, d.n_local - d.nh_pad_l, c->xhalo,
+    PLM_HIP(plm_launch_maxabs2(c->x + d.nh_pad_l, d.n_local - d.nh_pad_l, c->xhalo,
                                d.nx_halo * (int64_t)PLM_BLOCK_FLOATS(d), c->maxbits, c->jexp, d.jexp_bias, c->st));
-    HIP_TRY(plm_launch_expand(d, c->x, c->xhalo, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
+    PLM_HIP(plm_launch_expand(d, c->x, c->xhalo, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
     PLM_TRY(forward_at_x(c));
-    if (d.nblk_own > 0) HIP_TRY(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
-    HIP_TRY(plm_launch_pack_g(d, c->G, c->gsend, c->st));
+    if (d.nblk_own > 0) PLM_HIP(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
+    PLM_HIP(plm_launch_pack_g(d, c->G, c->gsend, c->st));
     PLM_TRY(ctx_collective(c, PLM_COLL_ALLTOALL, c->gsend, c->ghalo, c->g_send.data(), c->g_recv.data()));
     PLM_TRY(group_norms(c));
-    HIP_TRY(plm_launch_assemble(d, c->G, d.ksplit, c->ghalo, c->x, c->g, c->prob.lambda_h, c->prob.lambda_j,
+    PLM_HIP(plm_launch_assemble(d, c->G, d.ksplit, c->ghalo, c->x, c->g, c->prob.lambda_h, c->prob.lambda_j,
                                 c->reg_part, 0, 0.f, c->pair_n2, (float)c->prob.lambda_group, c->st));
-    HIP_TRY(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), nullptr, 0, c->reg_part, plm_reg_parts(d), c->scal,
+    PLM_HIP(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), nullptr, 0, c->reg_part, plm_reg_parts(d), c->scal,
                                  c->st));
     c->n_evals++;
     return PLM_OK;
@@ -454,19 +435,19 @@ int ctx_eval_enqueue_sharded(plm_ctx *c) {
 int ctx_eval_enqueue(plm_ctx *c) {
     const PlmDims &d = c->d;
     if (d.sharded) return ctx_eval_enqueue_sharded(c);
-    HIP_TRY(plm_launch_maxabs(d, c->x, c->maxbits, c->jexp, c->st));
-    HIP_TRY(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
+    PLM_HIP(plm_launch_maxabs(d, c->x, c->maxbits, c->jexp, c->st));
+    PLM_HIP(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
     PLM_TRY(forward_at_x(c));
-    HIP_TRY(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
+    PLM_HIP(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
     const void *Gsrc = c->G;
     int ks_count = d.ksplit, n_shard_nll = 0;
     const double *shard_nll = nullptr;
     if (d.nshards > 1) {
         const size_t slab = plm_slab_bytes(d);
         char *mine = (char *)c->gather + (size_t)d.shard * slab;
-        HIP_TRY(plm_launch_slab_reduce(d, c->G, (float *)mine, c->st));
-        HIP_TRY(plm_launch_partial_sum(c->fx_part, c->n_fx_part(), (double *)(mine + slab - 256), c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
+        PLM_HIP(plm_launch_slab_reduce(d, c->G, (float *)mine, c->st));
+        PLM_HIP(plm_launch_partial_sum(c->fx_part, c->n_fx_part(), (double *)(mine + slab - 256), c->st));
+        PLM_HIP(hipStreamSynchronize(c->st));
         if (!c->exchange) return fail(PLM_EINVAL, "n_shards > 1 but no exchange callback set");
         if (c->exchange(c->gather, slab, d.nshards, d.shard, c->exchange_user) != 0)
             return fail(PLM_ECALLBACK, "exchange callback failed");
@@ -476,9 +457,9 @@ int ctx_eval_enqueue(plm_ctx *c) {
         shard_nll = (const double *)((char *)c->gather + slab - 256);
     }
     PLM_TRY(group_norms(c));
-    HIP_TRY(plm_launch_assemble(d, Gsrc, ks_count, nullptr, c->x, c->g, c->prob.lambda_h, c->prob.lambda_j,
+    PLM_HIP(plm_launch_assemble(d, Gsrc, ks_count, nullptr, c->x, c->g, c->prob.lambda_h, c->prob.lambda_j,
                                 c->reg_part, 0, 0.f, c->pair_n2, (float)c->prob.lambda_group, c->st));
-    HIP_TRY(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), shard_nll, n_shard_nll, c->reg_part,
+    PLM_HIP(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), shard_nll, n_shard_nll, c->reg_part,
                                  plm_reg_parts(d), c->scal, c->st));
     c->n_evals++;
     return PLM_OK;
@@ -502,26 +483,26 @@ int vp_alloc(plm_ctx *c) {
     // column blocks are only a slice of them (h64 is filled and read for every site by forward_at_x)
     const size_t nsites = (size_t)std::max(std::max(1, (c->d.b16_hi - c->d.b16_lo) * 16),
                                            std::min(c->d.L, c->d.own_hi * 16) - c->d.h_site0);
-    PLM_TRY(dalloc((char **)&c->hj, plm_hj_bytes(c->d)));
-    PLM_TRY(dalloc((char **)&c->hpart, plm_hpart_bytes(c->d)));
-    PLM_TRY(dalloc((char **)&c->gpart, plm_gpart_bytes(c->d)));
-    PLM_TRY(dalloc((char **)&c->dpart, plm_gpart_bytes(c->d)));      // diagonal second-order sums: same shape
-    PLM_TRY(dalloc(&c->hg2, nsites));
-    PLM_TRY(dalloc(&c->hinv, nsites * c->d.Q * c->d.Q));
-    PLM_TRY(dalloc(&c->h64, 2 * plm_h64_stride(c->d)));
-    PLM_TRY(dalloc(&c->hcnt, plm_h64_stride(c->d)));
+    PLM_TRY(plm_dalloc((char **)&c->hj, plm_hj_bytes(c->d)));
+    PLM_TRY(plm_dalloc((char **)&c->hpart, plm_hpart_bytes(c->d)));
+    PLM_TRY(plm_dalloc((char **)&c->gpart, plm_gpart_bytes(c->d)));
+    PLM_TRY(plm_dalloc((char **)&c->dpart, plm_gpart_bytes(c->d)));      // diagonal second-order sums: same shape
+    PLM_TRY(plm_dalloc(&c->hg2, nsites));
+    PLM_TRY(plm_dalloc(&c->hinv, nsites * c->d.Q * c->d.Q));
+    PLM_TRY(plm_dalloc(&c->h64, 2 * plm_h64_stride(c->d)));
+    PLM_TRY(plm_dalloc(&c->hcnt, plm_h64_stride(c->d)));
     c->hcnt_valid = false;
-    PLM_TRY(dalloc((char **)&c->vp_flag, sizeof(PlmVpState)));
-    HIP_TRY(hipMemsetAsync(c->vp_flag, 0, sizeof(PlmVpState), c->st));
-    for (auto &e : c->vp_ev) HIP_TRY(hipEventCreate(&e));
-    for (auto &e : c->gemm_ev) HIP_TRY(hipEventCreate(&e));
+    PLM_TRY(plm_dalloc((char **)&c->vp_flag, sizeof(PlmVpState)));
+    PLM_HIP(hipMemsetAsync(c->vp_flag, 0, sizeof(PlmVpState), c->st));
+    for (auto &e : c->vp_ev) PLM_HIP(hipEventCreate(&e));
+    for (auto &e : c->gemm_ev) PLM_HIP(hipEventCreate(&e));
     c->vp_hess_age = -1;
     return PLM_OK;
 }
 // stage 1: forward GEMM (couplings of x) -> HJ
 int vp_counts(plm_ctx *c) {      // weighted state counts per site: once per set of weights
     if (!c->hcnt_valid) {
-        HIP_TRY(plm_launch_site_counts(c->d, c->msa_cm, c->w, c->hcnt, c->st));
+        PLM_HIP(plm_launch_site_counts(c->d, c->msa_cm, c->w, c->hcnt, c->st));
         c->hcnt_valid = true;
     }
     return PLM_OK;
@@ -531,16 +512,16 @@ int vp_stage1(plm_ctx *c) {
     PLM_TRY(vp_counts(c));
     if (d.sharded) {
         PLM_TRY(ctx_collective(c, PLM_COLL_ALLTOALL, x_rectangles(c), c->xhalo, c->x_send.data(), c->x_recv.data()));
-        HIP_TRY(plm_launch_maxabs2(c->x + d.nh_pad_l, d.n_local - d.nh_pad_l, c->xhalo,
+        PLM_HIP(plm_launch_maxabs2(c->x + d.nh_pad_l, d.n_local - d.nh_pad_l, c->xhalo,
                                    d.nx_halo * (int64_t)PLM_BLOCK_FLOATS(d), c->maxbits, c->jexp, d.jexp_bias, c->st));
-        HIP_TRY(plm_launch_expand(d, c->x, c->xhalo, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
+        PLM_HIP(plm_launch_expand(d, c->x, c->xhalo, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
     } else {
-        HIP_TRY(plm_launch_maxabs(d, c->x, c->maxbits, c->jexp, c->st));
-        HIP_TRY(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
+        PLM_HIP(plm_launch_maxabs(d, c->x, c->maxbits, c->jexp, c->st));
+        PLM_HIP(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
     }
-    if (c->gemm_ev[0]) HIP_TRY(hipEventRecord(c->gemm_ev[0], c->st));
-    HIP_TRY(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, c->fwd_accurate, c->st));
-    HIP_TRY(plm_launch_h64_init(d, c->x, c->h64, c->st));
+    if (c->gemm_ev[0]) PLM_HIP(hipEventRecord(c->gemm_ev[0], c->st));
+    PLM_HIP(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, c->fwd_accurate, c->st));
+    PLM_HIP(plm_launch_h64_init(d, c->x, c->h64, c->st));
     return PLM_OK;
 }
 // One Newton step on the fields with the cached (or, refresh: recomputed) inverse Hessians + the residual pass at the
@@ -550,14 +531,14 @@ int vp_step_and_residuals(plm_ctx *c, bool refresh) {
     const PlmDims &d = c->d;
     PLM_TRY(vp_counts(c));
     const int full = (refresh || c->vp_hess_age < 0) ? 1 : 0;
-    HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 0, full ? 2 : 1, c->fwd_accurate, nullptr, nullptr, c->hpart,
+    PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 0, full ? 2 : 1, c->fwd_accurate, nullptr, nullptr, c->hpart,
                              c->gpart, c->dpart, nullptr, PLM_VP_ALWAYS, c->st));
-    HIP_TRY(plm_launch_hsolve(d, c->hpart, c->gpart, full, c->x, c->h64, c->prob.lambda_h, 1, c->hinv, c->hg2, c->scal + 5, 0.0,
+    PLM_HIP(plm_launch_hsolve(d, c->hpart, c->gpart, full, c->x, c->h64, c->prob.lambda_h, 1, c->hinv, c->hg2, c->scal + 5, 0.0,
                               0.0, nullptr, 0, c->hcnt, c->dpart, c->st));
     if (full) c->vp_hess_age = 0;
-    HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
+    PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
                              nullptr, nullptr, PLM_VP_ALWAYS, c->st));
-    HIP_TRY(plm_launch_hsolve(d, c->hpart, c->gpart, 0, c->x, c->h64, c->prob.lambda_h, 0, c->hinv, c->hg2, c->scal + 5, 0.0,
+    PLM_HIP(plm_launch_hsolve(d, c->hpart, c->gpart, 0, c->x, c->h64, c->prob.lambda_h, 0, c->hinv, c->hg2, c->scal + 5, 0.0,
                               0.0, nullptr, 0, c->hcnt, c->dpart, c->st));
     return PLM_OK;
 }
@@ -578,11 +559,11 @@ int vp_chain(plm_ctx *c, int npos, int hess_upto, int expected_last, double tol2
         // Hessian sums: while the previous evaluation says the solver is still far (pos < hess_upto), whenever no
         // inverse exists yet, and at every position past the expected end (the cached inverses were not good enough)
         const bool hess = pos < hess_upto || pos > expected_last || c->vp_hess_age < 0;
-        HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 0, hess ? 2 : 1, c->fwd_accurate, nullptr, nullptr, c->hpart,
+        PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 0, hess ? 2 : 1, c->fwd_accurate, nullptr, nullptr, c->hpart,
                                  c->gpart, c->dpart, c->vp_flag, PLM_VP_PASS, c->st));
-        HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
+        PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
                                  nullptr, c->vp_flag, PLM_VP_PASS_RT, c->st));
-        HIP_TRY(plm_launch_hsolve(d, c->hpart, c->gpart, hess ? 2 : 0, c->x, c->h64, c->prob.lambda_h, 1, c->hinv, c->hg2,
+        PLM_HIP(plm_launch_hsolve(d, c->hpart, c->gpart, hess ? 2 : 0, c->x, c->h64, c->prob.lambda_h, 1, c->hinv, c->hg2,
                                   c->scal + 5, tol2, c->vp_floor2, c->vp_flag, 1, c->hcnt, c->dpart, c->st));
         // (whether the device RUNS this position is known only after the chain: ctx_eval_vp_finish resets the age of the
         // cached inverses if a Hessian position was among the passes executed -- ADVICE r5: resetting it here made the
@@ -601,20 +582,20 @@ int vp_stage3(plm_ctx *c, bool conditional, float *gout = nullptr, int mode = 2)
     // conditional: the backward GEMM runs only if the chain in front of it is done (PlmVpState::done is the first int
     // of the state) -- otherwise the host continues the chain and enqueues stage 3 again.  Not when sharded: every rank
     // takes part in the gradient-halo exchange of every stage 3, and the ranks' chains end independently.
-    if (c->gemm_ev[1]) HIP_TRY(hipEventRecord(c->gemm_ev[1], c->st));
+    if (c->gemm_ev[1]) PLM_HIP(hipEventRecord(c->gemm_ev[1], c->st));
     if (d.nblk_own > 0 || !d.sharded)
-        HIP_TRY(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, (conditional && !d.sharded) ? c->vp_flag : nullptr, c->st));
-    if (c->gemm_ev[2]) HIP_TRY(hipEventRecord(c->gemm_ev[2], c->st));
+        PLM_HIP(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, (conditional && !d.sharded) ? c->vp_flag : nullptr, c->st));
+    if (c->gemm_ev[2]) PLM_HIP(hipEventRecord(c->gemm_ev[2], c->st));
     if (d.sharded) {
-        HIP_TRY(plm_launch_pack_g(d, c->G, c->gsend, c->st));
+        PLM_HIP(plm_launch_pack_g(d, c->G, c->gsend, c->st));
         PLM_TRY(ctx_collective(c, PLM_COLL_ALLTOALL, c->gsend, c->ghalo, c->g_send.data(), c->g_recv.data()));
     }
     // mode 2: gradient of the reduced objective (field part zero), regulariser sums as usual
     PLM_TRY(group_norms(c));
-    HIP_TRY(plm_launch_assemble(d, c->G, d.ksplit, d.sharded ? c->ghalo : nullptr, c->x, gout, c->prob.lambda_h,
+    PLM_HIP(plm_launch_assemble(d, c->G, d.ksplit, d.sharded ? c->ghalo : nullptr, c->x, gout, c->prob.lambda_h,
                                 c->prob.lambda_j, c->reg_part, mode, 0.f, c->pair_n2, (float)c->prob.lambda_group, c->st));
     if (mode == 2)
-        HIP_TRY(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), nullptr, 0, c->reg_part, plm_reg_parts(d), c->scal,
+        PLM_HIP(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), nullptr, 0, c->reg_part, plm_reg_parts(d), c->scal,
                                      c->st));
     return PLM_OK;
 }
@@ -626,14 +607,14 @@ int ctx_eval_vp_enqueue(plm_ctx *c, double tol2) {
     const PlmDims &d = c->d;
     PLM_TRY(vp_stage1(c));
     if (c->vp_ev_pending) c->vp_ev_pending = false;     // (an evaluation nobody waited for: its events are re-recorded)
-    HIP_TRY(hipEventRecord(c->vp_ev[0], c->st));
+    PLM_HIP(hipEventRecord(c->vp_ev[0], c->st));
     // a chain expected to end on its first pass (late in a fit: the L-BFGS extrapolation of the fields is within the
     // tolerance) starts in the residual-writing role -- unless the cached inverse Hessians are due for their periodic
     // refresh (every 32 evaluations: a pass in that role carries no Hessian sums)
     const int c_prev = c->vp_c_prev;
     if (c->vp_hess_age >= 0) c->vp_hess_age++;
     const bool stale = c->vp_hess_age < 0 || c->vp_hess_age >= 32;
-    HIP_TRY(plm_launch_vp_reset(c->vp_flag, (c_prev == 0 && !stale) ? 1 : 0, c->scal + 5, c->st));
+    PLM_HIP(plm_launch_vp_reset(c->vp_flag, (c_prev == 0 && !stale) ? 1 : 0, c->scal + 5, c->st));
     c->vp_pos = 0;
     c->vp_extra = 0;
     c->vp_hess_mask = 0;
@@ -643,10 +624,10 @@ int ctx_eval_vp_enqueue(plm_ctx *c, double tol2) {
     int hess_upto = c_prev >= 2 ? c_prev : (stale ? 1 : 0);
     if (c->opt.vp_hess_pos >= 0) hess_upto = std::min(hess_upto, std::max(c->opt.vp_hess_pos, c->vp_hess_age < 0 ? 1 : 0));
     PLM_TRY(vp_chain(c, std::min(14, c_prev + 3), hess_upto, c_prev, tol2));
-    HIP_TRY(plm_launch_fields_to_x(d, c->h64, c->vp_flag, c->x, c->st));
-    HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr, nullptr,
+    PLM_HIP(plm_launch_fields_to_x(d, c->h64, c->vp_flag, c->x, c->st));
+    PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr, nullptr,
                              c->vp_flag, PLM_VP_FINAL, c->st));
-    HIP_TRY(hipEventRecord(c->vp_ev[1], c->st));
+    PLM_HIP(hipEventRecord(c->vp_ev[1], c->st));
     c->vp_ev_pending = true;
     PLM_TRY(vp_stage3(c, true));
     c->n_evals++;
@@ -715,31 +696,31 @@ int ctx_eval_vp_finish(plm_ctx *c, double tol2, bool *again, double *gh2_out) {
     // fields (unconditional) and stage 3 (unconditional)
     c->vp_last_gh2 = gh2;
     c->vp_extra++;
-    HIP_TRY(hipEventRecord(c->vp_ev[0], c->st));
-    HIP_TRY(hipMemsetAsync(c->scal + 5, 0, 3 * sizeof(double), c->st));
+    PLM_HIP(hipEventRecord(c->vp_ev[0], c->st));
+    PLM_HIP(hipMemsetAsync(c->scal + 5, 0, 3 * sizeof(double), c->st));
     if (gh2 > tol2) PLM_TRY(vp_chain(c, 6, 1 << 30, -1, tol2));
-    HIP_TRY(plm_launch_fields_to_x(d, c->h64, c->vp_flag, c->x, c->st));
-    HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
+    PLM_HIP(plm_launch_fields_to_x(d, c->h64, c->vp_flag, c->x, c->st));
+    PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
                              nullptr, c->vp_flag, PLM_VP_ALWAYS, c->st));
     // norm only (update = 0, not a chain position: k_vp_check writes the sum alone -- passes / verdict of the continued
     // chain stay), at the chain's current fields
-    HIP_TRY(plm_launch_hsolve(d, c->hpart, c->gpart, 0, c->x, c->h64, c->prob.lambda_h, 0, c->hinv, c->hg2, c->scal + 5, 0.0,
+    PLM_HIP(plm_launch_hsolve(d, c->hpart, c->gpart, 0, c->x, c->h64, c->prob.lambda_h, 0, c->hinv, c->hg2, c->scal + 5, 0.0,
                               0.0, c->vp_flag, 0, c->hcnt, c->dpart, c->st));
-    HIP_TRY(hipEventRecord(c->vp_ev[1], c->st));
+    PLM_HIP(hipEventRecord(c->vp_ev[1], c->st));
     c->vp_ev_pending = true;
     PLM_TRY(vp_stage3(c, false));
     *again = true;
     return PLM_OK;
 }
 int fetch_scalars(plm_ctx *c, int first, int count) {
-    HIP_TRY(hipMemcpyAsync(c->h_scal + first, c->scal + first, sizeof(double) * count, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemcpyAsync(c->h_scal + first, c->scal + first, sizeof(double) * count, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     return PLM_OK;
 }
 
 // scal slots: 0 fx, 1 nll, 2.. dot results
 int dots(plm_ctx *c, int npairs, const float *const *a, const float *const *b, int64_t n, int slot) {
-    HIP_TRY(plm_launch_dots(npairs, a, b, n, c->dot_scratch, c->scal + slot, c->st));
+    PLM_HIP(plm_launch_dots(npairs, a, b, n, c->dot_scratch, c->scal + slot, c->st));
     return PLM_OK;
 }
 
@@ -847,9 +828,9 @@ int set_start_point(plm_ctx *c) {
         for (int a = a0; a < d.Qc; a++) h[(size_t)(i - d.h_site0) * d.Q + a] = (float)(v[a] - mean);
     }
     c->eval_valid = false;
-    HIP_TRY(hipMemsetAsync(c->x, 0, sizeof(float) * d.n_local, c->st));
-    HIP_TRY(hipMemcpyAsync(c->x, h.data(), sizeof(float) * d.nh_pad_l, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemsetAsync(c->x, 0, sizeof(float) * d.n_local, c->st));
+    PLM_HIP(hipMemcpyAsync(c->x, h.data(), sizeof(float) * d.nh_pad_l, hipMemcpyHostToDevice, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     return PLM_OK;
 }
 
@@ -883,7 +864,7 @@ const char *plm_last_error(void) { return g_err.c_str(); }
 
 void plm_ctx_destroy(plm_ctx_t *c) {
     if (!c) return;
-    hipSetDevice(c->device);
+    (void)hipSetDevice(c->device);
     for (auto &e : c->gemm_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->vp_ev)
@@ -893,14 +874,20 @@ void plm_ctx_destroy(plm_ctx_t *c) {
                     c->canon, c->xhalo, c->ghalo, c->xsend, c->gsend, c->dinv, c->hj, c->hpart, c->gpart, c->dpart, c->hg2, c->hinv, c->h64, c->hcnt, c->vp_flag,
                     c->xa, c->ga, c->pair_n2};
     for (void *b : bufs)
-        if (b) hipFree(b);
-    if (c->h_scal) hipHostFree(c->h_scal);
+        if (b) (void)hipFree(b);
+    if (c->h_scal) (void)hipHostFree(c->h_scal);
     if (c->rccl) {
-        hipStreamSynchronize(c->st);
+        (void)hipStreamSynchronize(c->st);
         plm_rccl_destroy(c->rccl);
     }
     delete c;
 }
+
+// destroys the context when the scope ends, unless it was handed on (c = nullptr)
+struct CtxScope {
+    plm_ctx_t *c;
+    ~CtxScope() { plm_ctx_destroy(c); }
+};
 
 int plm_ctx_create(const plm_problem_t *prob, int device, void *stream, plm_ctx_t **out) {
     if (!prob || !out || !prob->msa) return fail(PLM_EINVAL, "NULL problem / msa / out");
@@ -934,17 +921,11 @@ int plm_ctx_create(const plm_problem_t *prob, int device, void *stream, plm_ctx_
     dmax.ksplit = std::max(c->ksplit_base, c->ksplit4);
     c->device = device;
     c->st = (hipStream_t)stream;
-    int rc = PLM_OK;
-    auto bail = [&](int code) {
-        plm_ctx_destroy(c);
-        return code;
-    };
+    CtxScope scope{c};
     // padded host image of the alignment, row-major; the column-major image (+ the "ones" block) is made from it on the
     // device (round 5: the strided host transposition was 25 ms of every context at the headline)
-    const size_t rm_rows = (size_t)d.Np + 32, cm_rows = (size_t)(d.nb16 + 1) * 16;
-    std::vector<int8_t> rm(rm_rows * d.Lp32, (int8_t)PLM_PAD_STATE);
-    for (int s = 0; s < d.N; s++) memcpy(&rm[(size_t)s * d.Lp32], prob->msa + (size_t)s * d.L, d.L);
-    const size_t cm_size = cm_rows * d.Np;
+    const size_t cm_rows = (size_t)(d.nb16 + 1) * 16, cm_size = cm_rows * d.Np;
+    const std::vector<int8_t> rm = padded_rows(d, prob->msa);
     {
         // Refuse a problem the device cannot hold BEFORE allocating: the runtime grants allocations beyond the HBM and the
         // failure would surface at some later launch.  What a fit holds: the operands of the two GEMMs, the stored
@@ -953,29 +934,30 @@ int plm_ctx_create(const plm_problem_t *prob, int device, void *stream, plm_ctx_
         const double need = (double)rm.size() + (double)cm_size + (double)plm_bt_bytes(d) + (double)plm_rt_bytes(dmax) +
                             (double)plm_g_bytes(dmax) + (vp_enabled(c) ? (double)plm_hj_bytes(d) : 0.0) +
                             4.0 * ((double)d.n_local * (2 * m + 5) + (double)d.n_canon + (double)d.L * d.L);
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > (double)free_b)
-            return bail(fail(PLM_ENOMEM, "the problem needs %.1f GB of device memory, %.1f GB are free (of %.1f GB)", need / 1e9,
-                             free_b / 1e9, total_b / 1e9));
+        PLM_TRY(plm_check_free(need, "the problem"));
     }
-    if ((rc = dalloc(&c->msa_rm, rm.size())) || (rc = dalloc(&c->msa_cm, cm_size)) ||
-        (rc = dalloc(&c->w, (size_t)d.Np)) || (rc = dalloc(&c->counts, (size_t)d.Np)) ||
-        (rc = dalloc((char **)&c->Bt, plm_bt_bytes(d))) || (rc = dalloc((char **)&c->Rt, plm_rt_bytes(dmax))) ||
-        (rc = dalloc((char **)&c->G, plm_g_bytes(dmax))) || (rc = dalloc(&c->fx_part, (size_t)c->n_fx_part())) ||
-        (rc = dalloc(&c->reg_part, (size_t)plm_reg_parts(d))) ||
-        (rc = dalloc(&c->dot_scratch, (size_t)4 * PLM_MAX_BASIS * PLM_DOT_BLOCKS)) ||
-        (rc = dalloc(&c->scal, (size_t)256)) ||
-        (rc = dalloc(&c->maxbits, (size_t)1)) || (rc = dalloc(&c->jexp, (size_t)1)) ||
-        (rc = dalloc(&c->x, (size_t)d.n_local)) || (rc = dalloc(&c->g, (size_t)d.n_local)) ||
-        (rc = dalloc(&c->canon, (size_t)d.n_canon + (size_t)d.L * d.L)))
-        return bail(rc);
-    if (d.nshards > 1 && !d.sharded && (rc = dalloc((char **)&c->gather, plm_slab_bytes(d) * d.nshards)))
-        return bail(rc);
+    PLM_TRY(plm_dalloc(&c->msa_rm, rm.size()));
+    PLM_TRY(plm_dalloc(&c->msa_cm, cm_size));
+    PLM_TRY(plm_dalloc(&c->w, (size_t)d.Np));
+    PLM_TRY(plm_dalloc(&c->counts, (size_t)d.Np));
+    PLM_TRY(plm_dalloc((char **)&c->Bt, plm_bt_bytes(d)));
+    PLM_TRY(plm_dalloc((char **)&c->Rt, plm_rt_bytes(dmax)));
+    PLM_TRY(plm_dalloc((char **)&c->G, plm_g_bytes(dmax)));
+    PLM_TRY(plm_dalloc(&c->fx_part, (size_t)c->n_fx_part()));
+    PLM_TRY(plm_dalloc(&c->reg_part, (size_t)plm_reg_parts(d)));
+    PLM_TRY(plm_dalloc(&c->dot_scratch, (size_t)4 * PLM_MAX_BASIS * PLM_DOT_BLOCKS));
+    PLM_TRY(plm_dalloc(&c->scal, (size_t)256));
+    PLM_TRY(plm_dalloc(&c->maxbits, (size_t)1));
+    PLM_TRY(plm_dalloc(&c->jexp, (size_t)1));
+    PLM_TRY(plm_dalloc(&c->x, (size_t)d.n_local));
+    PLM_TRY(plm_dalloc(&c->g, (size_t)d.n_local));
+    PLM_TRY(plm_dalloc(&c->canon, (size_t)d.n_canon + (size_t)d.L * d.L));
+    if (d.nshards > 1 && !d.sharded) PLM_TRY(plm_dalloc((char **)&c->gather, plm_slab_bytes(d) * d.nshards));
     if (d.sharded) {
         const size_t blk = PLM_BLOCK_FLOATS(d);
-        if ((rc = dalloc(&c->xhalo, (size_t)d.nx_halo * blk)) || (rc = dalloc(&c->gsend, (size_t)d.nx_halo * blk)) ||
-            (rc = dalloc(&c->ghalo, (size_t)d.ng_halo * blk)))
-            return bail(rc);
+        PLM_TRY(plm_dalloc(&c->xhalo, (size_t)d.nx_halo * blk));
+        PLM_TRY(plm_dalloc(&c->gsend, (size_t)d.nx_halo * blk));
+        PLM_TRY(plm_dalloc(&c->ghalo, (size_t)d.ng_halo * blk));
         // all-to-all byte counts: with shard r this shard shares the rectangle (own blocks) x (blocks of r); each of the
         // two owns half of its rows (plm_pair_owner), sends the couplings of its half and receives the partner's gradient
         // fragments for it
@@ -988,24 +970,20 @@ int plm_ctx_create(const plm_problem_t *prob, int device, void *stream, plm_ctx_
             c->x_recv[r] = c->g_send[r] = theirs * (int64_t)blk * 4;
         }
     }
-    hipError_t e;
-    if ((e = hipHostMalloc((void **)&c->h_scal, sizeof(double) * 256)) != hipSuccess)
-        return bail(fail(PLM_ENOMEM, "hipHostMalloc failed: %s", hipGetErrorString(e)));
-#define CT(expr)                                                                                  \
-    if ((e = (expr)) != hipSuccess)                                                               \
-        return bail(fail(e == hipErrorOutOfMemory ? PLM_ENOMEM : PLM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));
+    const hipError_t eh = hipHostMalloc((void **)&c->h_scal, sizeof(double) * 256);
+    if (eh != hipSuccess) return fail(PLM_ENOMEM, "hipHostMalloc failed: %s", hipGetErrorString(eh));
     // (a problem beyond the device may get its hipMallocs granted and meet hipErrorOutOfMemory only here, at the first
     // launch: tests/test_gpu_parity.py::test_a_problem_that_does_not_fit_the_device_is_refused_with_enomem)
-    CT(hipMemcpyAsync(c->msa_rm, rm.data(), rm.size(), hipMemcpyHostToDevice, c->st));
-    CT(plm_launch_msa_columns(d, c->msa_rm, c->msa_cm, (int)cm_rows, c->st));
-    CT(hipMemsetAsync(c->w, 0, sizeof(float) * d.Np, c->st));
-    CT(hipMemsetAsync(c->Rt, 0, plm_rt_bytes(dmax), c->st));
-    CT(hipMemsetAsync(c->x, 0, sizeof(float) * d.n_local, c->st));
-    CT(hipMemsetAsync(c->g, 0, sizeof(float) * d.n_local, c->st));
-    CT(hipMemsetAsync(c->scal, 0, sizeof(double) * 256, c->st));   // slots nobody writes still travel in all-reduces
-    if (c->gather) CT(hipMemsetAsync(c->gather, 0, plm_slab_bytes(d) * d.nshards, c->st));
-    CT(hipStreamSynchronize(c->st));
-#undef CT
+    PLM_HIP(hipMemcpyAsync(c->msa_rm, rm.data(), rm.size(), hipMemcpyHostToDevice, c->st));
+    PLM_HIP(plm_launch_msa_columns(d, c->msa_rm, c->msa_cm, (int)cm_rows, c->st));
+    PLM_HIP(hipMemsetAsync(c->w, 0, sizeof(float) * d.Np, c->st));
+    PLM_HIP(hipMemsetAsync(c->Rt, 0, plm_rt_bytes(dmax), c->st));
+    PLM_HIP(hipMemsetAsync(c->x, 0, sizeof(float) * d.n_local, c->st));
+    PLM_HIP(hipMemsetAsync(c->g, 0, sizeof(float) * d.n_local, c->st));
+    PLM_HIP(hipMemsetAsync(c->scal, 0, sizeof(double) * 256, c->st));   // slots nobody writes still travel in all-reduces
+    if (c->gather) PLM_HIP(hipMemsetAsync(c->gather, 0, plm_slab_bytes(d) * d.nshards, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
+    scope.c = nullptr;
     *out = c;
     return PLM_OK;
 }
@@ -1027,7 +1005,7 @@ int plm_ctx_set_collective(plm_ctx_t *c, plm_collective_cb collective, void *use
 int plm_ctx_attach_rccl(plm_ctx_t *c, const void *rccl_id) {
     if (!c || !rccl_id) return fail(PLM_EINVAL, "NULL ctx / id");
     if (c->rccl) return fail(PLM_EINVAL, "context already has a communicator");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     if (plm_rccl_init(rccl_id, c->d.nshards, c->d.shard, &c->rccl) != 0)
         return fail(PLM_ECALLBACK, "RCCL communicator of %d ranks: %s", c->d.nshards, plm_rccl_error());
     return PLM_OK;
@@ -1050,7 +1028,8 @@ int plm_rccl_selftest(int device, void *stream) {
     if (plm_rccl_init(id, 1, 0, &r) != 0) return fail(PLM_ECALLBACK, "%s", plm_rccl_error());
     const int n = 1000;
     double *buf = nullptr;
-    int rc = dalloc(&buf, (size_t)2 * n);
+    DeviceBuffers mem;
+    int rc = mem.alloc(&buf, (size_t)2 * n);
     std::vector<double> h(2 * n, 0.0), back(2 * n, -1.0);
     for (int k = 0; k < n; k++) h[k] = 0.5 * k - 7.0;
     const int64_t bytes = (int64_t)sizeof(double) * n, root = 0;
@@ -1073,7 +1052,7 @@ int plm_rccl_selftest(int device, void *stream) {
                 rc = fail(PLM_ECALLBACK, "one-rank collectives changed the data at %d", k);
                 break;
             }
-    if (buf) hipFree(buf);
+    mem.free_all();
     plm_rccl_destroy(r);
     return rc;
 }
@@ -1091,23 +1070,19 @@ int plm_rccl_probe(const void *rccl_id, int32_t nranks, int32_t rank, int device
     // device was lost in between.
     const int per = 128;                                   // doubles per peer message
     double *buf = nullptr;
-    PLM_TRY(dalloc(&buf, (size_t)(2 * nranks + 1) * per));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&buf, (size_t)(2 * nranks + 1) * per));
     std::vector<double> h((size_t)(2 * nranks + 1) * per, 0.0);
     for (int k = 0; k < nranks; k++)
         for (int j = 0; j < per; j++) h[(size_t)k * per + j] = 1000.0 * rank + k;          // message to rank k
     h[(size_t)2 * nranks * per] = 1.0 + rank;
     const std::vector<int64_t> counts((size_t)nranks, (int64_t)sizeof(double) * per);
     const int64_t one = sizeof(double);
-    if (hipMemcpyAsync(buf, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        hipFree(buf);
-        return fail(PLM_EDEVICE, "upload failed");
-    }
+    PLM_HIP(hipMemcpyAsync(buf, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+    PLM_HIP(hipStreamSynchronize(st));
     PlmRccl *r = nullptr;
-    if (plm_rccl_init(rccl_id, nranks, rank, &r) != 0) {
-        hipFree(buf);
+    if (plm_rccl_init(rccl_id, nranks, rank, &r) != 0)
         return fail(PLM_ECALLBACK, "RCCL communicator of %d ranks: %s", nranks, plm_rccl_error());
-    }
     int rc = PLM_OK;
     if (plm_rccl_collective(r, PLM_COLL_ALLTOALL, buf, buf + (size_t)nranks * per, counts.data(), counts.data(), st) != 0)
         rc = fail(PLM_ECALLBACK, "all-to-all: %s", plm_rccl_error());
@@ -1121,8 +1096,8 @@ int plm_rccl_probe(const void *rccl_id, int32_t nranks, int32_t rank, int device
         for (int k = 0; k < nranks && rc == PLM_OK; k++)
             if (h[(size_t)(nranks + k) * per] != 1000.0 * k + rank) rc = fail(PLM_ECALLBACK, "all-to-all delivered a wrong message from rank %d", k);
     }
-    hipStreamSynchronize(st);
-    hipFree(buf);
+    (void)hipStreamSynchronize(st);
+    mem.free_all();
     plm_rccl_destroy(r);
     return rc;
 }
@@ -1135,12 +1110,12 @@ int plm_rccl_probe_local(int32_t nranks, int device, void *stream) {
     if (plm_rccl_version() < 20000) return fail(PLM_ECALLBACK, "librccl not loadable: %s", plm_rccl_error());
     hipStream_t st = (hipStream_t)stream;
     double *buf = nullptr;
-    PLM_TRY(dalloc(&buf, (size_t)(2 * nranks + 1) * 128));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&buf, (size_t)(2 * nranks + 1) * 128));
     std::vector<double> h((size_t)(2 * nranks + 1) * 128, 1.0);
-    const bool ok = hipMemcpyAsync(buf, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
-                    hipStreamSynchronize(st) == hipSuccess;
-    hipFree(buf);
-    return ok ? PLM_OK : fail(PLM_EDEVICE, "upload failed");
+    PLM_HIP(hipMemcpyAsync(buf, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 int plm_ctx_set_options(plm_ctx_t *c, int32_t max_iter, double epsilon, int32_t lbfgs_m) {
@@ -1168,7 +1143,7 @@ int64_t plm_ctx_native_size(const plm_ctx_t *c) { return c ? c->d.n_local : 0; }
 
 int plm_ctx_set_weights(plm_ctx_t *c, const float *weights_host) {
     if (!c || !weights_host) return fail(PLM_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     const PlmDims &d = c->d;
     double neff = 0;
     float wmax = 0;
@@ -1181,9 +1156,9 @@ int plm_ctx_set_weights(plm_ctx_t *c, const float *weights_host) {
     // (rounds 1-2 limited the weights to < 4: the f16 planes of the residuals had a fixed 2^14 pre-scale.  The fixed-point
     // residuals of round 3 are scaled by the largest weight in use, any positive magnitude works.)
     if (!(neff > 0)) return fail(PLM_EINVAL, "sum of weights is zero");
-    HIP_TRY(hipMemsetAsync(c->w, 0, sizeof(float) * d.Np, c->st));
-    HIP_TRY(hipMemcpyAsync(c->w, weights_host, sizeof(float) * d.N, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemsetAsync(c->w, 0, sizeof(float) * d.Np, c->st));
+    PLM_HIP(hipMemcpyAsync(c->w, weights_host, sizeof(float) * d.N, hipMemcpyHostToDevice, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     c->n_eff = neff;
     c->have_weights = true;
     c->hcnt_valid = false;
@@ -1197,18 +1172,18 @@ int plm_ctx_set_weights(plm_ctx_t *c, const float *weights_host) {
 
 int plm_ctx_reweight(plm_ctx_t *c) {
     if (!c) return fail(PLM_EINVAL, "NULL ctx");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     const PlmDims &d = c->d;
     const int thresh = cluster_threshold(c->prob.theta_id, d.L, d.conv);
     std::vector<int32_t> counts(d.N);
     if (thresh <= 0) {
         std::fill(counts.begin(), counts.end(), d.N);  // every pair is a neighbour
-        HIP_TRY(hipMemcpyAsync(c->counts, counts.data(), sizeof(int32_t) * d.N, hipMemcpyHostToDevice, c->st));
+        PLM_HIP(hipMemcpyAsync(c->counts, counts.data(), sizeof(int32_t) * d.N, hipMemcpyHostToDevice, c->st));
     } else {
-        HIP_TRY(plm_launch_reweight(d, c->msa_rm, thresh, c->counts, c->st));
-        HIP_TRY(hipMemcpyAsync(counts.data(), c->counts, sizeof(int32_t) * d.N, hipMemcpyDeviceToHost, c->st));
+        PLM_HIP(plm_launch_reweight(d, c->msa_rm, thresh, c->counts, c->st));
+        PLM_HIP(hipMemcpyAsync(counts.data(), c->counts, sizeof(int32_t) * d.N, hipMemcpyDeviceToHost, c->st));
     }
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     std::vector<float> w(d.N);
     const float scale = c->prob.scale > 0 ? (float)c->prob.scale : 1.f;
     for (int s = 0; s < d.N; s++) {
@@ -1220,9 +1195,9 @@ int plm_ctx_reweight(plm_ctx_t *c) {
 
 int plm_ctx_get_weights(plm_ctx_t *c, float *weights_host, int32_t *counts_host, float *n_eff) {
     if (!c) return fail(PLM_EINVAL, "NULL ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    if (weights_host) HIP_TRY(hipMemcpy(weights_host, c->w, sizeof(float) * c->d.N, hipMemcpyDeviceToHost));
-    if (counts_host) HIP_TRY(hipMemcpy(counts_host, c->counts, sizeof(int32_t) * c->d.N, hipMemcpyDeviceToHost));
+    PLM_HIP(hipSetDevice(c->device));
+    if (weights_host) PLM_HIP(hipMemcpy(weights_host, c->w, sizeof(float) * c->d.N, hipMemcpyDeviceToHost));
+    if (counts_host) PLM_HIP(hipMemcpy(counts_host, c->counts, sizeof(int32_t) * c->d.N, hipMemcpyDeviceToHost));
     if (n_eff) *n_eff = (float)c->n_eff;
     return PLM_OK;
 }
@@ -1235,35 +1210,35 @@ static int ctx_marginals(plm_ctx_t *c, float *fi_host, float *fij_host, float *c
     if (!c->have_weights) return fail(PLM_EINVAL, "weights not set: call plm_ctx_reweight / plm_ctx_set_weights");
     if (c->d.nshards > 1) return fail(PLM_EUNSUPPORTED, "marginals run unsharded (create a 1-shard context)");
     c->eval_valid = false;   // g is used as scratch below
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     const PlmDims &d = c->d;
     // weighted one-hot Gram matrix through the backward GEMM: G = X^T diag(w) X
-    HIP_TRY(plm_launch_onehot_rt(d, c->msa_rm, c->w, c->Rt, c->st));
-    HIP_TRY(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
+    PLM_HIP(plm_launch_onehot_rt(d, c->msa_rm, c->w, c->Rt, c->st));
+    PLM_HIP(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
     // gap mode: raw weighted counts come back (factor 1) and are normalised per site / per pair over
     // the ungapped sequences on the host
-    HIP_TRY(plm_launch_assemble(d, c->G, d.ksplit, nullptr, c->g, c->g, 0.f, 0.f, c->reg_part, 1,
+    PLM_HIP(plm_launch_assemble(d, c->G, d.ksplit, nullptr, c->g, c->g, 0.f, 0.f, c->reg_part, 1,
                                 d.gap_mode ? 1.f : (float)(1.0 / c->n_eff), nullptr, 0.f, c->st));
-    HIP_TRY(plm_launch_native_to_canon(d, c->g, c->canon, c->st));
+    PLM_HIP(plm_launch_native_to_canon(d, c->g, c->canon, c->st));
     c->h_fi.resize((size_t)d.L * d.Qc);
-    HIP_TRY(hipMemcpyAsync(c->h_fi.data(), c->canon, sizeof(float) * d.L * d.Qc, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(c->h_fi.data(), c->canon, sizeof(float) * d.L * d.Qc, hipMemcpyDeviceToHost, c->st));
     // PLM_CONV_G_FREQ_TOTAL: normalised by N_eff (all sequences) instead of the ungapped ones
     const bool by_total = d.conv & PLM_CONV_G_FREQ_TOTAL;
     if (fij_host) {
         // gap mode: the pair blocks are normalised over the jointly ungapped sequences on the device (round 5; the host
         // loop over 44 850 blocks was 15 ms of a -g fit), same arithmetic: total in f64 in block order, (float)(f / total)
         if (d.gap_mode)
-            HIP_TRY(plm_launch_gap_normalise_pairs(d, c->canon + (size_t)d.L * d.Qc, by_total ? (double)c->n_eff : 0.0, c->st));
+            PLM_HIP(plm_launch_gap_normalise_pairs(d, c->canon + (size_t)d.L * d.Qc, by_total ? (double)c->n_eff : 0.0, c->st));
         if (compact && d.gap_mode) {
             const size_t npair = (size_t)d.L * (d.L - 1) / 2, qn = (size_t)d.Qc - 1;
-            HIP_TRY(plm_launch_compact_gap_blocks(d, c->canon + (size_t)d.L * d.Qc, compact, c->st));
-            HIP_TRY(hipMemcpyAsync(fij_host, compact, sizeof(float) * npair * qn * qn, hipMemcpyDeviceToHost, c->st));
+            PLM_HIP(plm_launch_compact_gap_blocks(d, c->canon + (size_t)d.L * d.Qc, compact, c->st));
+            PLM_HIP(hipMemcpyAsync(fij_host, compact, sizeof(float) * npair * qn * qn, hipMemcpyDeviceToHost, c->st));
         } else {
-            HIP_TRY(hipMemcpyAsync(fij_host, c->canon + (size_t)d.L * d.Qc,
+            PLM_HIP(hipMemcpyAsync(fij_host, c->canon + (size_t)d.L * d.Qc,
                                    sizeof(float) * (d.n_canon - (int64_t)d.L * d.Qc), hipMemcpyDeviceToHost, c->st));
         }
     }
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     if (d.gap_mode) {
         const int Q = d.Qc;
         for (int i = 0; i < d.L; i++) {
@@ -1281,13 +1256,13 @@ static int ctx_marginals(plm_ctx_t *c, float *fi_host, float *fij_host, float *c
 
 int plm_ctx_set_x(plm_ctx_t *c, const float *x_canonical_host) {
     if (!c) return fail(PLM_EINVAL, "NULL ctx");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     if (!x_canonical_host) return set_start_point(c);
     c->eval_valid = false;
     const PlmDims &d = c->d;
-    HIP_TRY(hipMemcpyAsync(c->canon, x_canonical_host, sizeof(float) * d.n_canon, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(plm_launch_canon_to_native(d, c->canon, c->x, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemcpyAsync(c->canon, x_canonical_host, sizeof(float) * d.n_canon, hipMemcpyHostToDevice, c->st));
+    PLM_HIP(plm_launch_canon_to_native(d, c->canon, c->x, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     return PLM_OK;
 }
 
@@ -1295,8 +1270,8 @@ int plm_ctx_set_x(plm_ctx_t *c, const float *x_canonical_host) {
 // shard contributes its own entries and an all-reduce (sum) puts the whole vector on every rank
 static int canon_full(plm_ctx_t *c, const float *native) {
     const PlmDims &d = c->d;
-    if (d.sharded) HIP_TRY(hipMemsetAsync(c->canon, 0, sizeof(float) * d.n_canon, c->st));
-    HIP_TRY(plm_launch_native_to_canon(d, native, c->canon, c->st));
+    if (d.sharded) PLM_HIP(hipMemsetAsync(c->canon, 0, sizeof(float) * d.n_canon, c->st));
+    PLM_HIP(plm_launch_native_to_canon(d, native, c->canon, c->st));
     if (d.sharded) {
         // all-gather of the parameter slices.  Every shard has written the entries IT owns into a zeroed canonical vector;
         // the sum over the shards is the whole vector on every rank (exact: every entry has one non-zero term).  (Round
@@ -1309,10 +1284,10 @@ static int canon_full(plm_ctx_t *c, const float *native) {
 }
 static int get_vec(plm_ctx_t *c, const float *native, float *out_host) {
     if (!c || !out_host) return fail(PLM_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     PLM_TRY(canon_full(c, native));
-    HIP_TRY(hipMemcpyAsync(out_host, c->canon, sizeof(float) * c->d.n_canon, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemcpyAsync(out_host, c->canon, sizeof(float) * c->d.n_canon, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     return PLM_OK;
 }
 // the same vector as two host arrays (fields [L][q], couplings [pairs][q][q]): what plm_fit hands back, without a
@@ -1320,21 +1295,21 @@ static int get_vec(plm_ctx_t *c, const float *native, float *out_host) {
 // compact (gap mode, PLM_FLAG_COMPACT_GAPS): device scratch; both arrays then come back in the (Q-1)-state layout
 static int get_vec_split(plm_ctx_t *c, const float *native, float *h_host, float *j_host, float *compact) {
     if (!c) return fail(PLM_EINVAL, "NULL ctx");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     PLM_TRY(canon_full(c, native));
     const PlmDims &d = c->d;
     const size_t nh = (size_t)d.L * d.Qc;
     const bool cut = compact && d.gap_mode;
     std::vector<float> hfull(cut && h_host ? nh : 0);
-    if (h_host) HIP_TRY(hipMemcpyAsync(cut ? hfull.data() : h_host, c->canon, sizeof(float) * nh, hipMemcpyDeviceToHost, c->st));
+    if (h_host) PLM_HIP(hipMemcpyAsync(cut ? hfull.data() : h_host, c->canon, sizeof(float) * nh, hipMemcpyDeviceToHost, c->st));
     if (j_host && cut) {
         const size_t npair = (size_t)d.L * (d.L - 1) / 2, qn = (size_t)d.Qc - 1;
-        HIP_TRY(plm_launch_compact_gap_blocks(d, c->canon + nh, compact, c->st));
-        HIP_TRY(hipMemcpyAsync(j_host, compact, sizeof(float) * npair * qn * qn, hipMemcpyDeviceToHost, c->st));
+        PLM_HIP(plm_launch_compact_gap_blocks(d, c->canon + nh, compact, c->st));
+        PLM_HIP(hipMemcpyAsync(j_host, compact, sizeof(float) * npair * qn * qn, hipMemcpyDeviceToHost, c->st));
     } else if (j_host) {
-        HIP_TRY(hipMemcpyAsync(j_host, c->canon + nh, sizeof(float) * ((size_t)d.n_canon - nh), hipMemcpyDeviceToHost, c->st));
+        PLM_HIP(hipMemcpyAsync(j_host, c->canon + nh, sizeof(float) * ((size_t)d.n_canon - nh), hipMemcpyDeviceToHost, c->st));
     }
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     if (cut && h_host)
         for (int i = 0; i < d.L; i++) memcpy(h_host + (size_t)i * (d.Qc - 1), &hfull[(size_t)i * d.Qc + 1], sizeof(float) * (d.Qc - 1));
     return PLM_OK;
@@ -1345,7 +1320,7 @@ int plm_ctx_get_g(plm_ctx_t *c, float *g_canonical_host) { return get_vec(c, c ?
 int plm_ctx_eval(plm_ctx_t *c, double *fx_out, double *nll_out) {
     if (!c) return fail(PLM_EINVAL, "NULL ctx");
     if (!c->have_weights) return fail(PLM_EINVAL, "weights not set");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     ctx_set_accurate(c, c->opt.fwd_mode != 0);    // a single evaluation is asked for its value: the accurate arithmetic
     PLM_TRY(ctx_eval_enqueue(c));
     if (c->d.sharded) PLM_TRY(ctx_allreduce_scalars(c, 0, 2));   // every shard must call eval together
@@ -1373,7 +1348,7 @@ int plm_ctx_eval(plm_ctx_t *c, double *fx_out, double *nll_out) {
 int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res) {
     if (!c) return fail(PLM_EINVAL, "NULL ctx");
     if (!c->have_weights) return fail(PLM_EINVAL, "weights not set");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     const double eps = c->prob.epsilon > 0 ? c->prob.epsilon : 1e-3;
     const double t0 = now_s();
     const PlmDims &d = c->d;
@@ -1402,7 +1377,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // {y_j, g}.  Opt-in (PLM_FLAG_PRECOND): measured to need MORE iterations than the scalar H0 at L = 300.
     const bool precond = (c->prob.flags & PLM_FLAG_PRECOND) && !c->h_fi.empty();
     if (precond) {
-        if (!c->dinv) PLM_TRY(dalloc(&c->dinv, (size_t)n));
+        if (!c->dinv) PLM_TRY(plm_dalloc(&c->dinv, (size_t)n));
         const size_t lq = (size_t)d.L * d.Q;
         std::vector<float> fv(2 * lq, 0.f);
         const int a0 = d.gap_mode;
@@ -1416,10 +1391,10 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             }
         }
         // staged through the gradient buffer's tail?  no: a small dedicated upload into canon (free during optimize)
-        HIP_TRY(hipMemcpyAsync(c->canon, fv.data(), sizeof(float) * fv.size(), hipMemcpyHostToDevice, c->st));
-        HIP_TRY(plm_launch_precond(d, c->canon, (float)c->n_eff, (float)c->prob.lambda_h, (float)c->prob.lambda_j,
+        PLM_HIP(hipMemcpyAsync(c->canon, fv.data(), sizeof(float) * fv.size(), hipMemcpyHostToDevice, c->st));
+        PLM_HIP(plm_launch_precond(d, c->canon, (float)c->n_eff, (float)c->prob.lambda_h, (float)c->prob.lambda_j,
                                    c->dinv, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));   // fv leaves scope
+        PLM_HIP(hipStreamSynchronize(c->st));   // fv leaves scope
     }
     const float *dinv = precond ? c->dinv : nullptr;
     // Gram matrix pieces, indexed by history slot: SY[i][j] = s_i.y_j, YDY[i][j] = y_i.D^-1 y_j, Sg = s_i.g,
@@ -1454,8 +1429,8 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
         for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B.v[B.n] = Y + (size_t)j * n; C.c[B.n++] = (float)cy[j]; }
         B.v[B.n] = c->g;
         C.c[B.n++] = (float)cg;
-        if (trial) HIP_TRY(plm_launch_multiaxpy_trial(c->dir, B, C, n, dinv, first_weighted, xacc, stp0, trial, c->st));
-        else HIP_TRY(plm_launch_multiaxpy(c->dir, B, C, n, dinv, first_weighted, c->st));
+        if (trial) PLM_HIP(plm_launch_multiaxpy_trial(c->dir, B, C, n, dinv, first_weighted, xacc, stp0, trial, c->st));
+        else PLM_HIP(plm_launch_multiaxpy(c->dir, B, C, n, dinv, first_weighted, c->st));
         return PLM_OK;
     };
 
@@ -1515,7 +1490,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             PlmVecList Qg, Bg;
             Qg.n = 1; Qg.v[0] = c->g;
             Bg.n = 2; Bg.v[0] = c->g; Bg.v[1] = c->g;
-            HIP_TRY(plm_launch_multidot(Qg, Bg, n, c->dot_scratch, c->scal + SL_MD, dinv, 1u, 1ull, c->st));   // gDg, gg
+            PLM_HIP(plm_launch_multidot(Qg, Bg, n, c->dot_scratch, c->scal + SL_MD, dinv, 1u, 1ull, c->st));   // gDg, gg
             PLM_TRY(norm_dots());
             PLM_TRY(ctx_allreduce_scalars(c, have ? SL_DG : 0, (have ? 8 - SL_DG : 8) + 2));
             PLM_TRY(fetch_scalars(c, 0, 10));
@@ -1548,8 +1523,8 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // pass, backward GEMM, assemble into the free direction vector); the fit ends only if THAT meets the rule, otherwise
     // it goes on with a target lowered by what the rounding costs.
     auto shipped_cond = [&](double *out) -> int {
-        HIP_TRY(plm_launch_h64_init(d, c->x, c->h64, c->st));
-        HIP_TRY(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr,
+        PLM_HIP(plm_launch_h64_init(d, c->x, c->h64, c->st));
+        PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr,
                                  nullptr, nullptr, PLM_VP_ALWAYS, c->st));
         PLM_TRY(vp_stage3(c, false, c->dir, 0));
         const float *a[1] = {c->dir};
@@ -1621,7 +1596,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                 // synchronisation (and, sharded, one all-reduce) per trial brings back f, the directional
                 // derivative and everything the next direction needs.
                 // (round 6: pair, Gram rows, g.p, x.x and the fields' x.x in ONE pass over the vectors)
-                HIP_TRY(plm_launch_sy_multidot(s_new, y_new, c->x, anchored ? c->xa : c->xp, c->g, anchored ? c->ga : c->gp,
+                PLM_HIP(plm_launch_sy_multidot(s_new, y_new, c->x, anchored ? c->xa : c->xp, c->g, anchored ? c->ga : c->gp,
                                                c->dir, B, n, d.nh_pad_l, c->dot_scratch, c->scal + SL_MD, c->scal + SL_DG, dinv,
                                                wq, wb, c->st));
                 PLM_TRY(ctx_allreduce_scalars(c, SL_FX, SL_MD + 3 * B.n + 1 - SL_FX));
@@ -1644,7 +1619,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                     (brackt && stmax - stmin <= xtol * stmax))
                     stp = stx;
                 if (!(count == 0 && (float)stp == stp0))      // the first trial point came with the direction
-                    HIP_TRY(plm_launch_lincomb(c->x, 1.f, c->xp, (float)stp, c->dir, n, c->st));
+                    PLM_HIP(plm_launch_lincomb(c->x, 1.f, c->xp, (float)stp, c->dir, n, c->st));
                 PLM_TRY(evaluate_trial());
                 double dg = c->h_scal[SL_DG];
                 fx = c->h_scal[SL_FX];
@@ -1812,11 +1787,11 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                 stored = std::min(stored, m - 1);
                 if (!anchored) {       // keep the point the pair started from: (xp, gp) is overwritten by the next swap
                     if (!c->xa) {
-                        PLM_TRY(dalloc(&c->xa, (size_t)n));
-                        PLM_TRY(dalloc(&c->ga, (size_t)n));
+                        PLM_TRY(plm_dalloc(&c->xa, (size_t)n));
+                        PLM_TRY(plm_dalloc(&c->ga, (size_t)n));
                     }
-                    HIP_TRY(hipMemcpyAsync(c->xa, c->xp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-                    HIP_TRY(hipMemcpyAsync(c->ga, c->gp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
+                    PLM_HIP(hipMemcpyAsync(c->xa, c->xp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
+                    PLM_HIP(hipMemcpyAsync(c->ga, c->gp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
                     anchored = true;
                 }
             } else {                   // slot e now holds a rejected pair: restart the history
@@ -1830,7 +1805,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             // fit and had no test: removed in round 6.)
         }
     }
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     c->eval_valid = true;   // every exit path above leaves the last accepted point in (x, g)
     c->hj_at_x = vp && status != PLM_STATUS_LINESEARCH;   // a failed line search ends on a rejected trial's potentials
     c->eval_vp = vp;
@@ -1864,7 +1839,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
 
 int plm_ctx_scores(plm_ctx_t *c, float *fn_host, float *cn_host) {
     if (!c || !fn_host || !cn_host) return fail(PLM_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     const PlmDims &d = c->d;
     float *fn_dev = c->canon + d.n_canon;
     PLM_TRY(canon_full(c, c->x));
@@ -1873,12 +1848,12 @@ int plm_ctx_scores(plm_ctx_t *c, float *fn_host, float *cn_host) {
     if (d.gap_mode) {
         // the zero-sum gauge and the norm are taken over the model's (Q-1) states only: k_fn leaves out row and column 0
         // of every block (round 5; rounds 2-4 repacked the blocks on the host: 54 ms of a -g fit at the headline)
-        HIP_TRY(plm_launch_fn(dc, c->canon + (size_t)d.L * d.Qc, fn_dev, 1, 1, c->st));
+        PLM_HIP(plm_launch_fn(dc, c->canon + (size_t)d.L * d.Qc, fn_dev, 1, 1, c->st));
     } else {
-        HIP_TRY(plm_launch_fn(dc, c->canon + (size_t)d.L * d.Qc, fn_dev, (d.conv & PLM_CONV_FN_NO_GAP) ? 1 : 0, 0, c->st));
+        PLM_HIP(plm_launch_fn(dc, c->canon + (size_t)d.L * d.Qc, fn_dev, (d.conv & PLM_CONV_FN_NO_GAP) ? 1 : 0, 0, c->st));
     }
-    HIP_TRY(hipMemcpyAsync(fn_host, fn_dev, sizeof(float) * d.L * d.L, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemcpyAsync(fn_host, fn_dev, sizeof(float) * d.L * d.L, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
     // APC (couplings/model.py:744-775): means over off-diagonal entries, diagonal blanked
     const int L = d.L;
     std::vector<double> col(L, 0.0);
@@ -1901,13 +1876,13 @@ int plm_ctx_time_field_positions(plm_ctx_t *c, int32_t reps, float *out_ms) {
     if (!c || !out_ms || reps <= 0) return fail(PLM_EINVAL, "bad argument");
     if (!c->have_weights) return fail(PLM_EINVAL, "weights not set");
     if (!vp_enabled(c) || !c->hj) return fail(PLM_EINVAL, "no stored potentials: plm_ctx_time_kernels on a variable-projection context first");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     const PlmDims &d = c->d;
     c->eval_valid = false;
     ctx_set_accurate(c, false);
     PLM_TRY(vp_counts(c));
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (auto &e : ev) PLM_HIP(hipEventCreate(&e));
     double acc[2] = {0, 0};
     int rc = PLM_OK;
     for (int r = 0; r < reps && rc == PLM_OK; r++) {
@@ -1941,56 +1916,56 @@ int plm_ctx_time_kernels(plm_ctx_t *c, int32_t reps, float *out_ms) {
     // one shard of the sharded-state mode can be timed alone (its kernels over its own site blocks; the halo buffers are
     // read as they are -- the collectives that fill them are not part of this measurement): scripts/shard_compute.py
     if (c->d.nshards > 1 && !c->d.sharded) return fail(PLM_EUNSUPPORTED, "kernel timing runs on 1-shard or sharded-state contexts");
-    HIP_TRY(hipSetDevice(c->device));
+    PLM_HIP(hipSetDevice(c->device));
     c->eval_valid = false;
     ctx_set_accurate(c, false);   // the evaluation pipeline is timed with the plain arithmetic (the exact forward GEMM separately)
     const PlmDims &d = c->d;
-    struct Events {   // destroyed on every exit path (HIP_TRY returns early)
+    struct Events {   // destroyed on every exit path (PLM_HIP returns early)
         hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         ~Events() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
     } evs;
     hipEvent_t (&ev)[6] = evs.e;
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (auto &e : ev) PLM_HIP(hipEventCreate(&e));
     double acc[PLM_K_COUNT] = {0};
     const bool vp = vp_enabled(c);
     if (vp) PLM_TRY(vp_alloc(c));
     for (int r = 0; r < reps; r++) {
         float ms;
-        HIP_TRY(hipEventRecord(ev[0], c->st));
+        PLM_HIP(hipEventRecord(ev[0], c->st));
         if (d.sharded) {
-            HIP_TRY(plm_launch_maxabs2(c->x + d.nh_pad_l, d.n_local - d.nh_pad_l, c->xhalo,
+            PLM_HIP(plm_launch_maxabs2(c->x + d.nh_pad_l, d.n_local - d.nh_pad_l, c->xhalo,
                                        d.nx_halo * (int64_t)PLM_BLOCK_FLOATS(d), c->maxbits, c->jexp, d.jexp_bias, c->st));
-            HIP_TRY(plm_launch_expand(d, c->x, c->xhalo, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
+            PLM_HIP(plm_launch_expand(d, c->x, c->xhalo, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
         } else {
-            HIP_TRY(plm_launch_maxabs(d, c->x, c->maxbits, c->jexp, c->st));
-            HIP_TRY(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
+            PLM_HIP(plm_launch_maxabs(d, c->x, c->maxbits, c->jexp, c->st));
+            PLM_HIP(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, c->fwd_accurate ? 1 : 0, c->st));
         }
-        HIP_TRY(hipEventRecord(ev[1], c->st));
+        PLM_HIP(hipEventRecord(ev[1], c->st));
         if (vp) {   // the fit's pipeline: forward GEMM -> HJ, 2 Newton steps on the fields, residual pass
-            HIP_TRY(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, 0, c->st));
-            HIP_TRY(hipEventRecord(ev[2], c->st));
+            PLM_HIP(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, 0, c->st));
+            PLM_HIP(hipEventRecord(ev[2], c->st));
             PLM_TRY(vp_step_and_residuals(c, r == 0));   // one Newton step + the residual pass
-            HIP_TRY(hipEventRecord(ev[5], c->st));
+            PLM_HIP(hipEventRecord(ev[5], c->st));
         } else {
             PLM_TRY(forward_at_x(c));
-            HIP_TRY(hipEventRecord(ev[2], c->st));
-            HIP_TRY(hipEventRecord(ev[5], c->st));
+            PLM_HIP(hipEventRecord(ev[2], c->st));
+            PLM_HIP(hipEventRecord(ev[5], c->st));
         }
-        if (d.nblk_own > 0 || !d.sharded) HIP_TRY(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
-        HIP_TRY(hipEventRecord(ev[3], c->st));
-        if (d.sharded) HIP_TRY(plm_launch_pack_g(d, c->G, c->gsend, c->st));
-        HIP_TRY(plm_launch_assemble(d, c->G, d.ksplit, d.sharded ? c->ghalo : nullptr, c->x, c->g, c->prob.lambda_h, c->prob.lambda_j,
+        if (d.nblk_own > 0 || !d.sharded) PLM_HIP(plm_launch_backward(d, c->msa_cm, c->Rt, c->G, nullptr, c->st));
+        PLM_HIP(hipEventRecord(ev[3], c->st));
+        if (d.sharded) PLM_HIP(plm_launch_pack_g(d, c->G, c->gsend, c->st));
+        PLM_HIP(plm_launch_assemble(d, c->G, d.ksplit, d.sharded ? c->ghalo : nullptr, c->x, c->g, c->prob.lambda_h, c->prob.lambda_j,
                                     c->reg_part, vp ? 2 : 0, 0.f, nullptr, 0.f, c->st));
-        HIP_TRY(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), nullptr, 0, c->reg_part, plm_reg_parts(d),
+        PLM_HIP(plm_launch_finish_fx(d, c->fx_part, c->n_fx_part(), nullptr, 0, c->reg_part, plm_reg_parts(d),
                                      c->scal, c->st));
-        HIP_TRY(hipEventRecord(ev[4], c->st));
-        HIP_TRY(hipEventSynchronize(ev[4]));
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); acc[PLM_K_EXPAND] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2])); acc[PLM_K_FORWARD] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[5])); acc[PLM_K_FIELDS] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[5], ev[3])); acc[PLM_K_BACKWARD] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[3], ev[4])); acc[PLM_K_ASSEMBLE] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[4])); acc[PLM_K_TOTAL] += ms;
+        PLM_HIP(hipEventRecord(ev[4], c->st));
+        PLM_HIP(hipEventSynchronize(ev[4]));
+        PLM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); acc[PLM_K_EXPAND] += ms;
+        PLM_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); acc[PLM_K_FORWARD] += ms;
+        PLM_HIP(hipEventElapsedTime(&ms, ev[2], ev[5])); acc[PLM_K_FIELDS] += ms;
+        PLM_HIP(hipEventElapsedTime(&ms, ev[5], ev[3])); acc[PLM_K_BACKWARD] += ms;
+        PLM_HIP(hipEventElapsedTime(&ms, ev[3], ev[4])); acc[PLM_K_ASSEMBLE] += ms;
+        PLM_HIP(hipEventElapsedTime(&ms, ev[0], ev[4])); acc[PLM_K_TOTAL] += ms;
     }
     {   // the L-BFGS vector kernels of one iteration with a full history of m = 6: trial point, pair + Gram pass, direction
         const int m = 6;
@@ -2006,44 +1981,44 @@ int plm_ctx_time_kernels(plm_ctx_t *c, int32_t reps, float *out_ms) {
         B.v[B.n++] = c->g;
         B.v[B.n++] = c->g;
         for (int i = 0; i < B.n; i++) C.c[i] = 0.f;
-        HIP_TRY(hipMemsetAsync(c->hist, 0, sizeof(float) * 2 * (size_t)m * n, c->st));
-        HIP_TRY(hipMemsetAsync(c->dir, 0, sizeof(float) * n, c->st));
-        HIP_TRY(hipMemcpyAsync(c->xp, c->x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-        HIP_TRY(hipMemcpyAsync(c->gp, c->g, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-        HIP_TRY(hipEventRecord(ev[0], c->st));
+        PLM_HIP(hipMemsetAsync(c->hist, 0, sizeof(float) * 2 * (size_t)m * n, c->st));
+        PLM_HIP(hipMemsetAsync(c->dir, 0, sizeof(float) * n, c->st));
+        PLM_HIP(hipMemcpyAsync(c->xp, c->x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
+        PLM_HIP(hipMemcpyAsync(c->gp, c->g, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
+        PLM_HIP(hipEventRecord(ev[0], c->st));
         for (int r = 0; r < reps; r++) {
             // as the optimiser issues them: pair + Gram rows + scalar products in one pass, direction + first trial point
-            HIP_TRY(plm_launch_sy_multidot(S, Y, c->x, c->xp, c->g, c->gp, c->dir, B, n, d.nh_pad_l, c->dot_scratch, c->scal + 8,
+            PLM_HIP(plm_launch_sy_multidot(S, Y, c->x, c->xp, c->g, c->gp, c->dir, B, n, d.nh_pad_l, c->dot_scratch, c->scal + 8,
                                            c->scal + 2, nullptr, 6u, 0ull, c->st));
             B.n -= 1;
-            HIP_TRY(plm_launch_multiaxpy_trial(c->dir, B, C, n, nullptr, m, c->xp, 0.f, c->x, c->st));
+            PLM_HIP(plm_launch_multiaxpy_trial(c->dir, B, C, n, nullptr, m, c->xp, 0.f, c->x, c->st));
             B.n += 1;
         }
-        HIP_TRY(hipEventRecord(ev[1], c->st));
-        HIP_TRY(hipEventSynchronize(ev[1]));
+        PLM_HIP(hipEventRecord(ev[1], c->st));
+        PLM_HIP(hipEventSynchronize(ev[1]));
         float ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        PLM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
         acc[PLM_K_LBFGS_VECTOR] = ms;
-        HIP_TRY(hipMemsetAsync(c->hist, 0, sizeof(float) * 2 * (size_t)m * n, c->st));
+        PLM_HIP(hipMemsetAsync(c->hist, 0, sizeof(float) * 2 * (size_t)m * n, c->st));
     }
     if (vp && !d.sharded) {   // the exact forward GEMM (last iterations of a fit, plm_eval), on its own operand
         float ms;
-        HIP_TRY(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, 1, c->st));
-        HIP_TRY(hipEventRecord(ev[0], c->st));
-        for (int r = 0; r < reps; r++) HIP_TRY(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, 1, c->st));
-        HIP_TRY(hipEventRecord(ev[1], c->st));
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        PLM_HIP(plm_launch_expand(d, c->x, nullptr, c->jexp, c->Bt, 1, c->st));
+        PLM_HIP(hipEventRecord(ev[0], c->st));
+        for (int r = 0; r < reps; r++) PLM_HIP(plm_launch_forward_store(d, c->msa_rm, c->Bt, c->jexp, c->hj, 1, c->st));
+        PLM_HIP(hipEventRecord(ev[1], c->st));
+        PLM_HIP(hipEventSynchronize(ev[1]));
+        PLM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
         acc[PLM_K_FORWARD_ACCURATE] = ms;
     }
     {
         const int thresh = cluster_threshold(c->prob.theta_id, d.L, d.conv);
-        HIP_TRY(hipEventRecord(ev[0], c->st));
-        HIP_TRY(plm_launch_reweight(d, c->msa_rm, std::max(1, thresh), c->counts, c->st));
-        HIP_TRY(hipEventRecord(ev[1], c->st));
-        HIP_TRY(hipEventSynchronize(ev[1]));
+        PLM_HIP(hipEventRecord(ev[0], c->st));
+        PLM_HIP(plm_launch_reweight(d, c->msa_rm, std::max(1, thresh), c->counts, c->st));
+        PLM_HIP(hipEventRecord(ev[1], c->st));
+        PLM_HIP(hipEventSynchronize(ev[1]));
         float ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        PLM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
         acc[PLM_K_REWEIGHT] = ms * reps;
     }
     for (int k = 0; k < PLM_K_COUNT; k++) out_ms[k] = (float)(acc[k] / reps);
@@ -2090,22 +2065,20 @@ int plm_reweight_ex(const int8_t *msa, int32_t n_seqs, int32_t n_sites, double t
     PLM_TRY(check_device(0));
     PlmDims d;
     PLM_TRY(make_dims(p, plm_options_from_env(), &d));
-    const size_t rm_rows = (size_t)d.Np + 32;
-    std::vector<int8_t> rm(rm_rows * d.Lp32, (int8_t)PLM_PAD_STATE);
-    for (int s = 0; s < d.N; s++) memcpy(&rm[(size_t)s * d.Lp32], msa + (size_t)s * d.L, d.L);
+    const std::vector<int8_t> rm = padded_rows(d, msa);
     int8_t *dev = nullptr;
     int32_t *cnt = nullptr;
-    PLM_TRY(dalloc(&dev, rm.size()));
-    int rc = dalloc(&cnt, (size_t)d.Np);
-    if (rc) { hipFree(dev); return rc; }
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&dev, rm.size()));
+    PLM_TRY(mem.alloc(&cnt, (size_t)d.Np));
     const int thresh = cluster_threshold(theta_id, d.L, d.conv);
-    hipError_t e = hipMemcpy(dev, rm.data(), rm.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && thresh > 0) e = plm_launch_reweight(d, dev, thresh, cnt, nullptr);
-    if (e == hipSuccess && thresh > 0) e = hipMemcpy(counts_out, cnt, sizeof(int32_t) * d.N, hipMemcpyDeviceToHost);
-    if (thresh <= 0) std::fill(counts_out, counts_out + d.N, d.N);
-    hipFree(dev);
-    hipFree(cnt);
-    if (e != hipSuccess) return fail(PLM_EDEVICE, "reweight failed: %s", hipGetErrorString(e));
+    PLM_HIP(hipMemcpy(dev, rm.data(), rm.size(), hipMemcpyHostToDevice));
+    if (thresh > 0) {
+        PLM_HIP(plm_launch_reweight(d, dev, thresh, cnt, nullptr));
+        PLM_HIP(hipMemcpy(counts_out, cnt, sizeof(int32_t) * d.N, hipMemcpyDeviceToHost));
+    } else {
+        std::fill(counts_out, counts_out + d.N, d.N);
+    }
     return PLM_OK;
 }
 
@@ -2155,15 +2128,13 @@ int plm_scores_ex(const float *jij, int32_t n_sites, int32_t n_states, int32_t f
     d.Q = n_states;
     const size_t nj = (size_t)n_sites * (n_sites - 1) / 2 * n_states * n_states;
     float *dj = nullptr, *dfn = nullptr;
-    PLM_TRY(dalloc(&dj, nj));
-    int rc = dalloc(&dfn, (size_t)n_sites * n_sites);
-    if (rc) { hipFree(dj); return rc; }
-    hipError_t e = hipMemcpy(dj, jij, sizeof(float) * nj, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = plm_launch_fn(d, dj, dfn, (flags & PLM_CONV_FN_NO_GAP) ? 1 : 0, 0, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(fn_out, dfn, sizeof(float) * n_sites * n_sites, hipMemcpyDeviceToHost);
-    hipFree(dj);
-    hipFree(dfn);
-    if (e != hipSuccess) return fail(PLM_EDEVICE, "scores failed: %s", hipGetErrorString(e));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&dj, nj));
+    PLM_TRY(mem.alloc(&dfn, (size_t)n_sites * n_sites));
+    PLM_HIP(hipMemcpy(dj, jij, sizeof(float) * nj, hipMemcpyHostToDevice));
+    PLM_HIP(plm_launch_fn(d, dj, dfn, (flags & PLM_CONV_FN_NO_GAP) ? 1 : 0, 0, nullptr));
+    PLM_HIP(hipMemcpy(fn_out, dfn, sizeof(float) * n_sites * n_sites, hipMemcpyDeviceToHost));
+    mem.free_all();
     const int L = n_sites;
     std::vector<double> col(L, 0.0);
     double tot = 0;
@@ -2197,9 +2168,7 @@ static int energies_impl(const int8_t *seqs, int32_t n, int32_t L, int32_t q, co
     for (size_t k = 0; k < (size_t)n * L; k++)
         if (seqs[k] < 0 || seqs[k] >= q) return fail(PLM_EINVAL, "seqs[%zu] = %d outside 0..%d", k, (int)seqs[k], q - 1);
     hipStream_t st = (hipStream_t)stream;
-    const size_t rm_rows = (size_t)d.Np + 32;
-    std::vector<int8_t> rm(rm_rows * d.Lp32, (int8_t)PLM_PAD_STATE);
-    for (int s = 0; s < d.N; s++) memcpy(&rm[(size_t)s * d.Lp32], seqs + (size_t)s * d.L, d.L);
+    const std::vector<int8_t> rm = padded_rows(d, seqs);
     const int nblk = d.b16_hi - d.b16_lo;
     const int ngrp = plm_fwd_groups(d.Q, 0);     // energy partials per (sequence, site block, state group)
     const size_t out_dev_floats = potentials ? (size_t)d.N * d.L * d.Qc : (size_t)d.Np * nblk * ngrp * 2;
@@ -2209,38 +2178,30 @@ static int energies_impl(const int8_t *seqs, int32_t n, int32_t L, int32_t q, co
     uint32_t *maxbits = nullptr;
     int32_t *jexp = nullptr;
     double *en = nullptr;
-    auto cleanup = [&](int code) {
-        void *all[] = {msa_rm, canon, x, outd, Bt, maxbits, jexp, en};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    int rc;
-    if ((rc = dalloc(&msa_rm, rm.size())) || (rc = dalloc(&canon, (size_t)d.n_canon)) ||
-        (rc = dalloc(&x, (size_t)d.n_native)) || (rc = dalloc(&outd, out_dev_floats)) ||
-        (rc = dalloc(&Bt, plm_bt_bytes(d))) || (rc = dalloc(&maxbits, (size_t)1)) || (rc = dalloc(&jexp, (size_t)1)) ||
-        (rc = dalloc(&en, (size_t)d.N * 3)))
-        return cleanup(rc);
-    hipError_t e;
-#define ET(expr)                                                                                   \
-    if ((e = (expr)) != hipSuccess)                                                                \
-        return cleanup(fail(e == hipErrorOutOfMemory ? PLM_ENOMEM : PLM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));
-    ET(hipMemcpyAsync(msa_rm, rm.data(), rm.size(), hipMemcpyHostToDevice, st));
-    ET(hipMemcpyAsync(canon, x_canon, sizeof(float) * d.n_canon, hipMemcpyHostToDevice, st));
-    ET(hipMemsetAsync(x, 0, sizeof(float) * d.n_native, st));
-    ET(plm_launch_canon_to_native(d, canon, x, st));
-    ET(plm_launch_maxabs(d, x, maxbits, jexp, st));
-    ET(plm_launch_expand(d, x, nullptr, jexp, Bt, accurate, st));
-    ET(plm_launch_forward_energy(d, msa_rm, Bt, x, jexp, potentials, accurate, outd, st));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&msa_rm, rm.size()));
+    PLM_TRY(mem.alloc(&canon, (size_t)d.n_canon));
+    PLM_TRY(mem.alloc(&x, (size_t)d.n_native));
+    PLM_TRY(mem.alloc(&outd, out_dev_floats));
+    PLM_TRY(mem.alloc(&Bt, plm_bt_bytes(d)));
+    PLM_TRY(mem.alloc(&maxbits, (size_t)1));
+    PLM_TRY(mem.alloc(&jexp, (size_t)1));
+    PLM_TRY(mem.alloc(&en, (size_t)d.N * 3));
+    PLM_HIP(hipMemcpyAsync(msa_rm, rm.data(), rm.size(), hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemcpyAsync(canon, x_canon, sizeof(float) * d.n_canon, hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemsetAsync(x, 0, sizeof(float) * d.n_native, st));
+    PLM_HIP(plm_launch_canon_to_native(d, canon, x, st));
+    PLM_HIP(plm_launch_maxabs(d, x, maxbits, jexp, st));
+    PLM_HIP(plm_launch_expand(d, x, nullptr, jexp, Bt, accurate, st));
+    PLM_HIP(plm_launch_forward_energy(d, msa_rm, Bt, x, jexp, potentials, accurate, outd, st));
     if (potentials) {
-        ET(hipMemcpyAsync(out_host, outd, sizeof(float) * out_dev_floats, hipMemcpyDeviceToHost, st));
+        PLM_HIP(hipMemcpyAsync(out_host, outd, sizeof(float) * out_dev_floats, hipMemcpyDeviceToHost, st));
     } else {
-        ET(plm_launch_energy_sum(d, outd, en, st));
-        ET(hipMemcpyAsync(out_host, en, sizeof(double) * (size_t)d.N * 3, hipMemcpyDeviceToHost, st));
+        PLM_HIP(plm_launch_energy_sum(d, outd, en, st));
+        PLM_HIP(hipMemcpyAsync(out_host, en, sizeof(double) * (size_t)d.N * 3, hipMemcpyDeviceToHost, st));
     }
-    ET(hipStreamSynchronize(st));
-#undef ET
-    return cleanup(PLM_OK);
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 int plm_hamiltonians(const int8_t *seqs, int32_t n, int32_t n_sites, int32_t n_states, const float *x_canonical,
@@ -2260,33 +2221,25 @@ int plm_meanfield(const int8_t *msa, int32_t n_seqs, int32_t n_sites, int32_t n_
     p.theta_id = theta_id;
     plm_ctx_t *c = nullptr;
     PLM_TRY(plm_ctx_create(&p, device, stream, &c));
+    CtxScope scope{c};                       // destroyed after the buffers below are freed
     const PlmDims d = c->d;
     const size_t lq = (size_t)d.L * d.Qc, pq = (size_t)d.L * (d.L - 1) / 2 * d.Qc * d.Qc, llqq = lq * lq;
     double *hi = nullptr, *jfull = nullptr, *di = nullptr;
     float *jp = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {hi, jfull, di, jp};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        plm_ctx_destroy(c);
-        return code;
-    };
-    int rc = plm_ctx_reweight(c);
-    if (!rc) rc = plm_ctx_get_weights(c, out->weights, nullptr, &out->n_eff);
-    if (!rc) rc = plm_ctx_marginals(c, out->fi, out->fij);      // leaves [f_i | f_ij blocks] in c->canon
-    if (rc) return done(rc);
-    if ((out->hi && (rc = dalloc(&hi, lq))) || (out->jij_full && (rc = dalloc(&jfull, llqq))) ||
-        (out->di && (rc = dalloc(&di, (size_t)d.L * d.L))) || (out->jij && (rc = dalloc(&jp, pq))))
-        return done(rc);
-    rc = plm_meanfield_device(c->canon, c->canon + lq, d.L, d.Qc, pseudo_count, c->st, hi, jfull, jp, di);
-    if (rc) return done(rc);
-    hipError_t e = hipSuccess;
-    if (hi && e == hipSuccess) e = hipMemcpy(out->hi, hi, sizeof(double) * lq, hipMemcpyDeviceToHost);
-    if (jfull && e == hipSuccess) e = hipMemcpy(out->jij_full, jfull, sizeof(double) * llqq, hipMemcpyDeviceToHost);
-    if (di && e == hipSuccess) e = hipMemcpy(out->di, di, sizeof(double) * (size_t)d.L * d.L, hipMemcpyDeviceToHost);
-    if (jp && e == hipSuccess) e = hipMemcpy(out->jij, jp, sizeof(float) * pq, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(fail(PLM_EDEVICE, "download of the mean-field result failed: %s", hipGetErrorString(e)));
-    return done(PLM_OK);
+    PLM_TRY(plm_ctx_reweight(c));
+    PLM_TRY(plm_ctx_get_weights(c, out->weights, nullptr, &out->n_eff));
+    PLM_TRY(plm_ctx_marginals(c, out->fi, out->fij));      // leaves [f_i | f_ij blocks] in c->canon
+    DeviceBuffers mem;
+    if (out->hi) PLM_TRY(mem.alloc(&hi, lq));
+    if (out->jij_full) PLM_TRY(mem.alloc(&jfull, llqq));
+    if (out->di) PLM_TRY(mem.alloc(&di, (size_t)d.L * d.L));
+    if (out->jij) PLM_TRY(mem.alloc(&jp, pq));
+    PLM_TRY(plm_meanfield_device(c->canon, c->canon + lq, d.L, d.Qc, pseudo_count, c->st, hi, jfull, jp, di));
+    if (hi) PLM_HIP(hipMemcpy(out->hi, hi, sizeof(double) * lq, hipMemcpyDeviceToHost));
+    if (jfull) PLM_HIP(hipMemcpy(out->jij_full, jfull, sizeof(double) * llqq, hipMemcpyDeviceToHost));
+    if (di) PLM_HIP(hipMemcpy(out->di, di, sizeof(double) * (size_t)d.L * d.L, hipMemcpyDeviceToHost));
+    if (jp) PLM_HIP(hipMemcpy(out->jij, jp, sizeof(float) * pq, hipMemcpyDeviceToHost));
+    return PLM_OK;
 }
 
 int plm_direct_information(const double *jij_full, const double *fi, int32_t n_sites, int32_t n_states, int device,
@@ -2295,21 +2248,15 @@ int plm_direct_information(const double *jij_full, const double *fi, int32_t n_s
     PLM_TRY(check_device(device));
     const size_t L = (size_t)n_sites, q = (size_t)n_states;
     double *J = nullptr, *f = nullptr, *di = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {J, f, di};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    int rc;
-    if ((rc = dalloc(&J, L * L * q * q)) || (rc = dalloc(&f, L * q)) || (rc = dalloc(&di, L * L))) return done(rc);
-    hipError_t e = hipMemcpy(J, jij_full, sizeof(double) * L * L * q * q, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(f, fi, sizeof(double) * L * q, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(fail(PLM_EDEVICE, "upload failed: %s", hipGetErrorString(e)));
-    rc = plm_direct_information_device(J, f, n_sites, n_states, (hipStream_t)stream, di);
-    if (rc) return done(rc);
-    e = hipMemcpy(di_out, di, sizeof(double) * L * L, hipMemcpyDeviceToHost);
-    return done(e == hipSuccess ? PLM_OK : fail(PLM_EDEVICE, "download failed: %s", hipGetErrorString(e)));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&J, L * L * q * q));
+    PLM_TRY(mem.alloc(&f, L * q));
+    PLM_TRY(mem.alloc(&di, L * L));
+    PLM_HIP(hipMemcpy(J, jij_full, sizeof(double) * L * L * q * q, hipMemcpyHostToDevice));
+    PLM_HIP(hipMemcpy(f, fi, sizeof(double) * L * q, hipMemcpyHostToDevice));
+    PLM_TRY(plm_direct_information_device(J, f, n_sites, n_states, (hipStream_t)stream, di));
+    PLM_HIP(hipMemcpy(di_out, di, sizeof(double) * L * L, hipMemcpyDeviceToHost));
+    return PLM_OK;
 }
 
 int plm_alignment_stats(const int8_t *msa, int32_t n, int32_t L, int32_t gap_state, const int8_t *query,
@@ -2326,26 +2273,20 @@ int plm_alignment_stats(const int8_t *msa, int32_t n, int32_t L, int32_t gap_sta
     hipStream_t st = (hipStream_t)stream;
     int8_t *dm = nullptr, *dq = nullptr;
     int32_t *dsg = nullptr, *dcg = nullptr, *did = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {dm, dq, dsg, dcg, did};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    int rc;
-    if ((rc = dalloc(&dm, (size_t)n * L + 16)) || (query && (rc = dalloc(&dq, (size_t)L))) ||
-        (seq_gaps && (rc = dalloc(&dsg, (size_t)n))) || (col_gaps && (rc = dalloc(&dcg, (size_t)L))) ||
-        (ident && (rc = dalloc(&did, (size_t)n))))
-        return done(rc);
-    hipError_t e = hipMemcpyAsync(dm, msa, (size_t)n * L, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && query) e = hipMemcpyAsync(dq, query, (size_t)L, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = plm_launch_align_stats(dm, n, L, gap_state, dq, dsg, dcg, did, st);
-    if (e == hipSuccess && seq_gaps) e = hipMemcpyAsync(seq_gaps, dsg, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && col_gaps) e = hipMemcpyAsync(col_gaps, dcg, sizeof(int32_t) * L, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && ident) e = hipMemcpyAsync(ident, did, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(fail(PLM_EDEVICE, "alignment statistics failed: %s", hipGetErrorString(e)));
-    return done(PLM_OK);
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&dm, (size_t)n * L + 16));
+    if (query) PLM_TRY(mem.alloc(&dq, (size_t)L));
+    if (seq_gaps) PLM_TRY(mem.alloc(&dsg, (size_t)n));
+    if (col_gaps) PLM_TRY(mem.alloc(&dcg, (size_t)L));
+    if (ident) PLM_TRY(mem.alloc(&did, (size_t)n));
+    PLM_HIP(hipMemcpyAsync(dm, msa, (size_t)n * L, hipMemcpyHostToDevice, st));
+    if (query) PLM_HIP(hipMemcpyAsync(dq, query, (size_t)L, hipMemcpyHostToDevice, st));
+    PLM_HIP(plm_launch_align_stats(dm, n, L, gap_state, dq, dsg, dcg, did, st));
+    if (seq_gaps) PLM_HIP(hipMemcpyAsync(seq_gaps, dsg, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (col_gaps) PLM_HIP(hipMemcpyAsync(col_gaps, dcg, sizeof(int32_t) * L, hipMemcpyDeviceToHost, st));
+    if (ident) PLM_HIP(hipMemcpyAsync(ident, did, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 static int fit_impl(const plm_problem_t *problem, plm_result_t *result, int device, void *stream, plm_iter_cb iter_cb,
@@ -2363,7 +2304,6 @@ static int fit_impl(const plm_problem_t *problem, plm_result_t *result, int devi
     PLM_TRY(plm_ctx_create(&p1, device, stream, &c1));
     int rc = PLM_OK;
     const int N = problem->n_seqs, L = problem->n_sites, q = problem->n_states;
-    const size_t npq = (size_t)L * (L - 1) / 2 * q * q;
     std::vector<float> w(N), fi((size_t)L * q);
     double t1 = now_s();
     rc = plm_ctx_reweight(c1);
@@ -2374,9 +2314,9 @@ static int fit_impl(const plm_problem_t *problem, plm_result_t *result, int devi
     // PLM_FLAG_COMPACT_GAPS: the pair arrays lose the gap state's row and column on the device, before the download
     const bool compact = (problem->flags & PLM_FLAG_COMPACT_GAPS) && (problem->flags & PLM_FLAG_IGNORE_GAPS);
     float *cbuf = nullptr;
-    if (!rc && compact && (result->fij || result->jij) && q > 1 &&
-        hipMalloc((void **)&cbuf, sizeof(float) * (size_t)L * (L - 1) / 2 * (q - 1) * (q - 1) + 16) != hipSuccess)
-        rc = fail(PLM_ENOMEM, "out of device memory (gap compaction buffer)");
+    DeviceBuffers mem;
+    if (!rc && compact && (result->fij || result->jij) && q > 1)
+        rc = mem.alloc(&cbuf, (size_t)L * (L - 1) / 2 * (q - 1) * (q - 1) + 4);
     if (!rc) rc = ctx_marginals(c1, fi.data(), result->fij, cbuf);
     result->seconds_marginals = now_s() - t1;
     plm_ctx_t *c = c1;
@@ -2395,7 +2335,7 @@ static int fit_impl(const plm_problem_t *problem, plm_result_t *result, int devi
     if (!rc) rc = plm_ctx_set_x(c, nullptr);
     if (!rc) rc = plm_ctx_optimize(c, iter_cb, iter_user, result);
     if (!rc && (result->hi || result->jij)) rc = get_vec_split(c, c->x, result->hi, result->jij, cbuf);
-    if (cbuf) (void)hipFree(cbuf);
+    mem.free_all();
     if (!rc && (result->fn || result->cn)) {   // either score matrix may be asked for on its own
         std::vector<float> spare;
         float *fn = result->fn, *cn = result->cn;

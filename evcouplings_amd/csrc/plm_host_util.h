@@ -1,0 +1,101 @@
+// plm_host_util.h -- the host-side plumbing every one-shot entry point of the library shares: the message recorder and
+// the device check of plm_host.cpp, one error macro for HIP calls, a scope guard for device memory, the free-memory
+// check that precedes the allocations, and the few size expressions the entry points have in common.  Host code only.
+#pragma once
+#include "../../include/plm_hip.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
+
+int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
+int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
+
+// plm_meanfield.hip.  fi (L q raw frequencies), fij (raw i<j blocks) and the outputs are device pointers; any output may
+// be null: hi [L q] f64, jfull [L L q q] f64, jpairs [pairs q q] f32, di [L L] f64.
+int plm_meanfield_device(const float *fi, const float *fij, int L, int q, double pseudo_count, hipStream_t st,
+                         double *hi, double *jfull, float *jpairs, double *di);
+int plm_direct_information_device(const double *jdense, const double *rfi, int L, int q, hipStream_t st, double *di);
+
+// A HIP call that must succeed: the message names the call and carries HIP's text; out of memory is PLM_ENOMEM (the
+// runtime grants allocations beyond the HBM, and the failure then surfaces at a later call), everything else PLM_EDEVICE.
+#define PLM_HIP(expr)                                                                                      \
+    do {                                                                                                   \
+        const hipError_t e__ = (expr);                                                                     \
+        if (e__ != hipSuccess)                                                                             \
+            return plm_fail(e__ == hipErrorOutOfMemory ? PLM_ENOMEM : PLM_EDEVICE, "%s failed: %s (%s:%d)", \
+                            #expr, hipGetErrorString(e__), __FILE__, __LINE__);                            \
+    } while (0)
+
+#define PLM_TRY(expr)                  \
+    do {                               \
+        int rc__ = (expr);             \
+        if (rc__ != PLM_OK) return rc__; \
+    } while (0)
+
+// n_elems of T on the device, 16 bytes at least; the caller owns the pointer (the members of a context)
+template <typename T> int plm_dalloc(T **p, size_t n_elems) {
+    void *b = nullptr;
+    const hipError_t e = hipMalloc(&b, std::max<size_t>(n_elems * sizeof(T), 16));
+    *p = e == hipSuccess ? (T *)b : nullptr;
+    if (e != hipSuccess)
+        return plm_fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed: %s", n_elems * sizeof(T), hipGetErrorString(e));
+    return PLM_OK;
+}
+
+// The device buffers (and at most one pinned host buffer) of one call: freed when the scope ends, or at free_all().
+struct DeviceBuffers {
+    std::vector<void *> dev;
+    void *pinned = nullptr;
+    DeviceBuffers() = default;
+    DeviceBuffers(const DeviceBuffers &) = delete;
+    DeviceBuffers &operator=(const DeviceBuffers &) = delete;
+    ~DeviceBuffers() { free_all(); }
+    template <typename T> int alloc(T **p, size_t n_elems) {
+        const int rc = plm_dalloc(p, n_elems);
+        if (rc == PLM_OK) dev.push_back(*p);
+        return rc;
+    }
+    template <typename T> int alloc_pinned(T **p, size_t n_elems) {
+        const hipError_t e = pinned ? hipErrorInvalidValue : hipHostMalloc(&pinned, n_elems * sizeof(T));
+        *p = e == hipSuccess ? (T *)pinned : nullptr;
+        if (e != hipSuccess)
+            return plm_fail(PLM_ENOMEM, "hipHostMalloc of %zu bytes failed: %s", n_elems * sizeof(T), hipGetErrorString(e));
+        return PLM_OK;
+    }
+    void free_all() {
+        for (void *b : dev) (void)hipFree(b);
+        dev.clear();
+        if (pinned) (void)hipHostFree(pinned);
+        pinned = nullptr;
+    }
+};
+
+// PLM_ENOMEM before any allocation when the call needs more device memory than is free.  table_bytes: the share of the
+// expanded couplings of the sweep kernels, named in the message when it is given.
+inline int plm_check_free(double need_bytes, const char *what, double table_bytes = 0) {
+    size_t free_b = 0, total_b = 0;
+    const hipError_t e = hipMemGetInfo(&free_b, &total_b);
+    if (e != hipSuccess) return plm_fail(PLM_EDEVICE, "hipMemGetInfo failed: %s", hipGetErrorString(e));
+    if (need_bytes <= (double)free_b) return PLM_OK;
+    char share[64] = "";
+    if (table_bytes > 0) snprintf(share, sizeof share, " (%.2f GB of it the expanded couplings)", table_bytes / 1e9);
+    return plm_fail(PLM_ENOMEM, "%s needs %.2f GB of device memory%s, %.2f GB are free (of %.1f GB)", what,
+                    need_bytes / 1e9, share, free_b / 1e9, total_b / 1e9);
+}
+
+// entries of the canonical layout, L q fields and the i<j blocks of q q couplings.  A double: the sizes are compared
+// with the free memory before anything is known to fit a size_t (exact wherever the call goes on)
+inline double plm_n_canon(int L, int q) { return (double)L * q + (double)L * (L - 1) / 2 * q * q; }
+
+inline uint32_t plm_state_mask(int q) { return q == 32 ? 0xFFFFFFFFu : (1u << q) - 1u; }   // states 0 .. q-1
+
+// The padded row-major host image of n sequences of L states that the forward kernels read: rows of row_len bytes,
+// n_rows of them, `pad` wherever no sequence is.
+inline std::vector<int8_t> plm_padded_rows(const int8_t *seqs, int n, int L, size_t n_rows, size_t row_len, int8_t pad) {
+    std::vector<int8_t> rm(n_rows * row_len, pad);
+    for (int s = 0; s < n; s++) memcpy(&rm[(size_t)s * row_len], seqs + (size_t)s * L, L);
+    return rm;
+}

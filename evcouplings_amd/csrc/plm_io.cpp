@@ -15,8 +15,7 @@
 
 #include "../../include/plm_hip.h"
 #include "plm_internal.h"
-
-int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
+#include "plm_host_util.h"
 
 namespace {
 inline bool is_ws(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13); }

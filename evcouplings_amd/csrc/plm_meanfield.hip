@@ -12,12 +12,10 @@
 // on one tiled f64 GEMM kernel: rocSOLVER does the same in one call, but loading its 0.9 GB library costs
 // ~230 s on a fresh MI355X box (measured), against 0.1 s for the whole mean-field run at L = 300.
 #include "plm_internal.h"
-#include "../../include/plm_hip.h"
+#include "plm_host_util.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
-
-int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
 
 namespace {
 
@@ -263,7 +261,10 @@ __global__ __launch_bounds__(256) void k_zero_upper_blocks(double *__restrict__ 
 // A (np x np, SPD) -> A^-1 in place (full symmetric storage).  X, D: scratch np x np and nb x 64 x 64.
 int spd_inverse(hipStream_t st, double *A, int np, double *X, double *D, int *info) {
     const int nb = np / MF_NB;
-    (void)hipMemsetAsync(info, 0, sizeof(int), st);
+    DeviceBuffers mem;
+    double *T = nullptr;
+    PLM_TRY(mem.alloc(&T, (size_t)MF_NB * np));
+    PLM_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
     // 1. A = L L^T, right-looking by block columns
     for (int k = 0; k < nb; k++) {
         double *Akk = A + ((size_t)k * np + k) * MF_NB;
@@ -273,8 +274,8 @@ int spd_inverse(hipStream_t st, double *A, int np, double *X, double *D, int *in
             double *Aik = A + ((size_t)(k + 1) * MF_NB) * np + (size_t)k * MF_NB;   // panel below the diagonal block
             // L_ik = A_ik L_kk^-T = A_ik (Dinv_k)^T : out of place through X's first columns, then copied back
             dgemm<0, 1>(st, rest, MF_NB, MF_NB, 1.0, Aik, np, D + (size_t)k * MF_NB * MF_NB, MF_NB, 0.0, X, MF_NB);
-            (void)hipMemcpy2DAsync(Aik, sizeof(double) * np, X, sizeof(double) * MF_NB, sizeof(double) * MF_NB, rest,
-                                   hipMemcpyDeviceToDevice, st);
+            PLM_HIP(hipMemcpy2DAsync(Aik, sizeof(double) * np, X, sizeof(double) * MF_NB, sizeof(double) * MF_NB, rest,
+                                     hipMemcpyDeviceToDevice, st));
             // trailing matrix -= L_panel L_panel^T (whole square: the upper part is never read)
             double *A22 = A + ((size_t)(k + 1) * MF_NB) * np + (size_t)(k + 1) * MF_NB;
             dgemm<0, 1>(st, rest, rest, MF_NB, -1.0, Aik, np, Aik, np, 1.0, A22, np);
@@ -282,12 +283,10 @@ int spd_inverse(hipStream_t st, double *A, int np, double *X, double *D, int *in
     }
     hipLaunchKernelGGL(k_zero_upper_blocks, dim3((unsigned)(((int64_t)np * np + 255) / 256)), dim3(256), 0, st, A, np);
     // 2. X = L^-1 by block rows: X_ii = Dinv_i, X_i,<i = -Dinv_i (L_i,<i X_<i,<i)
-    (void)hipMemsetAsync(X, 0, sizeof(double) * (size_t)np * np, st);
-    double *T = nullptr;
-    if (hipMalloc((void **)&T, sizeof(double) * (size_t)MF_NB * np) != hipSuccess) return PLM_ENOMEM;
+    PLM_HIP(hipMemsetAsync(X, 0, sizeof(double) * (size_t)np * np, st));
     for (int i = 0; i < nb; i++) {
-        (void)hipMemcpy2DAsync(X + ((size_t)i * np + i) * MF_NB, sizeof(double) * np, D + (size_t)i * MF_NB * MF_NB,
-                               sizeof(double) * MF_NB, sizeof(double) * MF_NB, MF_NB, hipMemcpyDeviceToDevice, st);
+        PLM_HIP(hipMemcpy2DAsync(X + ((size_t)i * np + i) * MF_NB, sizeof(double) * np, D + (size_t)i * MF_NB * MF_NB,
+                                 sizeof(double) * MF_NB, sizeof(double) * MF_NB, MF_NB, hipMemcpyDeviceToDevice, st));
         if (i > 0) {
             const int w = i * MF_NB;
             dgemm<0, 0>(st, MF_NB, w, w, 1.0, A + (size_t)i * MF_NB * np, np, X, np, 0.0, T, np);
@@ -297,66 +296,55 @@ int spd_inverse(hipStream_t st, double *A, int np, double *X, double *D, int *in
     }
     // 3. A^-1 = X^T X
     dgemm<1, 0>(st, np, np, np, 1.0, X, np, X, np, 0.0, A, np);
-    hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(T);
-    return e == hipSuccess ? PLM_OK : PLM_EDEVICE;
+    PLM_HIP(hipGetLastError());
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 }  // namespace
 
-// Device part of plm_meanfield: fi (L*q raw frequencies) and fij (raw i<j blocks) are device pointers.
-// Outputs are device pointers too (any of them may be null): hi [L*q] f64, jfull [L*L*q*q] f64,
-// jpairs [pairs*q*q] f32, di [L*L] f64.
+// Device part of plm_meanfield (the contract is at the declaration, plm_host_util.h)
 int plm_meanfield_device(const float *fi, const float *fij, int L, int q, double pseudo_count, hipStream_t st,
                          double *hi, double *jfull, float *jpairs, double *di) {
     if (q < 2 || q > 32) return plm_fail(PLM_EUNSUPPORTED, "mean-field DCA supports 2..32 states");
     const int n = L * (q - 1), np = (n + MF_NB - 1) / MF_NB * MF_NB;
     double *C = nullptr, *X = nullptr, *D = nullptr;
     int *info = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {C, X, D, info};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    if (hipMalloc((void **)&C, sizeof(double) * (size_t)np * np) != hipSuccess ||
-        hipMalloc((void **)&X, sizeof(double) * (size_t)np * np) != hipSuccess ||
-        hipMalloc((void **)&D, sizeof(double) * (size_t)np * MF_NB) != hipSuccess ||
-        hipMalloc((void **)&info, sizeof(int)) != hipSuccess)
-        return done(plm_fail(PLM_ENOMEM, "hipMalloc of the %d x %d covariance matrix failed", np, np));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&C, (size_t)np * np));
+    PLM_TRY(mem.alloc(&X, (size_t)np * np));
+    PLM_TRY(mem.alloc(&D, (size_t)np * MF_NB));
+    PLM_TRY(mem.alloc(&info, 1));
     const int64_t nn = (int64_t)np * np;
     hipLaunchKernelGGL(k_mf_cov, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, fi, fij, L, q, pseudo_count, np, C);
-    if (hipGetLastError() != hipSuccess) return done(plm_fail(PLM_EDEVICE, "k_mf_cov launch failed"));
-    int rc = spd_inverse(st, C, np, X, D, info);
-    if (rc) return done(plm_fail(rc, "the covariance inverse failed on the device"));
+    PLM_HIP(hipGetLastError());
+    PLM_TRY(spd_inverse(st, C, np, X, D, info));
     int hinfo = 0;
-    if (hipMemcpy(&hinfo, info, sizeof hinfo, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(plm_fail(PLM_EDEVICE, "reading the factorisation status failed"));
+    PLM_HIP(hipMemcpy(&hinfo, info, sizeof hinfo, hipMemcpyDeviceToHost));
     if (hinfo)
-        return done(plm_fail(PLM_EINVAL, "covariance matrix is not positive definite (pivot %d); raise the pseudo-count",
-                             hinfo));
+        return plm_fail(PLM_EINVAL, "covariance matrix is not positive definite (pivot %d); raise the pseudo-count", hinfo);
     if (jfull || jpairs) {
         const int64_t tot = (int64_t)L * L * q * q;
         hipLaunchKernelGGL(k_mf_extract, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, C, np, L, q, jfull, jpairs);
     }
     if (hi) hipLaunchKernelGGL(k_mf_fields, dim3(L * q), dim3(256), 0, st, C, np, fi, L, q, pseudo_count, hi);
     if (di) {
-        (void)hipMemsetAsync(di, 0, sizeof(double) * (size_t)L * L, st);
+        PLM_HIP(hipMemsetAsync(di, 0, sizeof(double) * (size_t)L * L, st));
         hipLaunchKernelGGL(k_mf_di, dim3((unsigned)((int64_t)L * (L - 1) / 2)), dim3(64), 0, st, C, np, fi, L, q,
                            pseudo_count, (const double *)nullptr, (const double *)nullptr, di);
     }
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return done(plm_fail(PLM_EDEVICE, "mean-field kernels failed"));
-    return done(PLM_OK);
+    PLM_HIP(hipGetLastError());
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 // direct information from given couplings and (regularised) frequencies -- device pointers
 int plm_direct_information_device(const double *jdense, const double *rfi, int L, int q, hipStream_t st, double *di) {
     if (q < 2 || q > 32) return plm_fail(PLM_EUNSUPPORTED, "direct information supports 2..32 states");
-    (void)hipMemsetAsync(di, 0, sizeof(double) * (size_t)L * L, st);
+    PLM_HIP(hipMemsetAsync(di, 0, sizeof(double) * (size_t)L * L, st));
     hipLaunchKernelGGL(k_mf_di, dim3((unsigned)((int64_t)L * (L - 1) / 2)), dim3(64), 0, st, (const double *)nullptr, 0,
                        (const float *)nullptr, L, q, 0.0, jdense, rfi, di);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return plm_fail(PLM_EDEVICE, "k_mf_di failed");
+    PLM_HIP(hipGetLastError());
+    PLM_HIP(hipStreamSynchronize(st));
     return PLM_OK;
 }

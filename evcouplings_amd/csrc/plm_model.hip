@@ -7,13 +7,10 @@
 // Everything is float64, like the model's arrays.  Pair blocks arrive compact: the i<j blocks of the dense
 // [L][L][q][q] array in row-major pair order (plm_pair_index), uploaded as the L-1 contiguous row tails J[i, i+1:].
 #include "plm_internal.h"
-#include "../../include/plm_hip.h"
+#include "plm_host_util.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-
-int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
-int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
 
 namespace {
 
@@ -181,32 +178,13 @@ __global__ __launch_bounds__(64) void k_independent_fields(const double *__restr
 }
 
 // L-1 copies of the row tails J[i, i+1:] of a dense [L][L][q][q] host array into the compact pair buffer
-hipError_t upload_pairs(const double *dense, int L, int q, double *dev, hipStream_t st) {
+int upload_pairs(const double *dense, int L, int q, double *dev, hipStream_t st) {
     const size_t qq = (size_t)q * q;
     size_t off = 0;
     for (int i = 0; i < L - 1; i++) {
         const size_t n = (size_t)(L - 1 - i) * qq;
-        hipError_t e = hipMemcpyAsync(dev + off, dense + ((size_t)i * L + i + 1) * qq, sizeof(double) * n,
-                                      hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
+        PLM_HIP(hipMemcpyAsync(dev + off, dense + ((size_t)i * L + i + 1) * qq, sizeof(double) * n, hipMemcpyHostToDevice, st));
         off += n;
-    }
-    return hipSuccess;
-}
-
-// PLM_ENOMEM before any allocation when the call needs more device memory than is free (as plm_ctx_create does)
-int check_free(double need, const char *what) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > (double)free_b)
-        return plm_fail(PLM_ENOMEM, "%s needs %.2f GB of device memory, %.2f GB are free (of %.1f GB)", what, need / 1e9,
-                        free_b / 1e9, total_b / 1e9);
-    return PLM_OK;
-}
-
-template <typename T> int dmalloc(T **p, size_t n) {
-    if (hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        return plm_fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed", n * sizeof(T));
     }
     return PLM_OK;
 }
@@ -228,71 +206,59 @@ int plm_model_pair_scores_ex(const double *jij_full, const double *fij_full, con
                              int32_t n_states, int32_t flags, int device, void *stream, double *fn_out, double *mi_out) {
     if (flags & ~PLM_MODEL_FI_PRODUCT_F32) return plm_fail(PLM_EINVAL, "unknown flags 0x%x", flags);
     if (!jij_full || !fij_full || !fi || !fn_out || !mi_out) return plm_fail(PLM_EINVAL, "NULL argument");
-    int rc = check_shape(n_sites, n_states);
-    if (rc) return rc;
-    if ((rc = plm_check_device(device))) return rc;
+    PLM_TRY(check_shape(n_sites, n_states));
+    PLM_TRY(plm_check_device(device));
     const int L = n_sites, q = n_states;
     const size_t P = (size_t)L * (L - 1) / 2, qq = (size_t)q * q, LL = (size_t)L * L;
-    if ((rc = check_free(8.0 * (2.0 * P * qq + (double)L * q + 2.0 * LL), "pair scores"))) return rc;
+    PLM_TRY(plm_check_free(8.0 * (2.0 * P * qq + (double)L * q + 2.0 * LL), "pair scores"));
     hipStream_t st = (hipStream_t)stream;
     double *J = nullptr, *F = nullptr, *f = nullptr, *fn = nullptr, *mi = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {J, F, f, fn, mi};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    if ((rc = dmalloc(&J, P * qq)) || (rc = dmalloc(&F, P * qq)) || (rc = dmalloc(&f, (size_t)L * q)) ||
-        (rc = dmalloc(&fn, LL)) || (rc = dmalloc(&mi, LL)))
-        return done(rc);
-    hipError_t e = upload_pairs(jij_full, L, q, J, st);
-    if (e == hipSuccess) e = upload_pairs(fij_full, L, q, F, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(f, fi, sizeof(double) * L * q, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(fn, 0, sizeof(double) * LL, st);
-    if (e == hipSuccess) e = hipMemsetAsync(mi, 0, sizeof(double) * LL, st);
-    if (e != hipSuccess) return done(plm_fail(PLM_EDEVICE, "upload failed: %s", hipGetErrorString(e)));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&J, P * qq));
+    PLM_TRY(mem.alloc(&F, P * qq));
+    PLM_TRY(mem.alloc(&f, (size_t)L * q));
+    PLM_TRY(mem.alloc(&fn, LL));
+    PLM_TRY(mem.alloc(&mi, LL));
+    PLM_TRY(upload_pairs(jij_full, L, q, J, st));
+    PLM_TRY(upload_pairs(fij_full, L, q, F, st));
+    PLM_HIP(hipMemcpyAsync(f, fi, sizeof(double) * L * q, hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemsetAsync(fn, 0, sizeof(double) * LL, st));
+    PLM_HIP(hipMemsetAsync(mi, 0, sizeof(double) * LL, st));
     hipLaunchKernelGGL(k_model_pair_scores, dim3((unsigned)P), dim3(64), 0, st, J, F, f, L, q, (flags & PLM_MODEL_FI_PRODUCT_F32) ? 1 : 0, fn, mi);
-    if ((e = hipGetLastError()) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "k_model_pair_scores launch failed"));
-    e = hipMemcpyAsync(fn_out, fn, sizeof(double) * LL, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mi_out, mi, sizeof(double) * LL, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return done(e == hipSuccess ? PLM_OK : plm_fail(PLM_EDEVICE, "pair scores failed: %s", hipGetErrorString(e)));
+    PLM_HIP(hipGetLastError());
+    PLM_HIP(hipMemcpyAsync(fn_out, fn, sizeof(double) * LL, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipMemcpyAsync(mi_out, mi, sizeof(double) * LL, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 int plm_double_mutants(const double *jij_full, const double *smm, const int8_t *target, int32_t n_sites,
                        int32_t n_states, int device, void *stream, double *dmm_out) {
     if (!jij_full || !smm || !target || !dmm_out) return plm_fail(PLM_EINVAL, "NULL argument");
-    int rc = check_shape(n_sites, n_states);
-    if (rc) return rc;
+    PLM_TRY(check_shape(n_sites, n_states));
     const int L = n_sites, q = n_states;
     for (int k = 0; k < L; k++)
         if (target[k] < 0 || target[k] >= q)
             return plm_fail(PLM_EINVAL, "target[%d] = %d outside 0..%d", k, (int)target[k], q - 1);
-    if ((rc = plm_check_device(device))) return rc;
+    PLM_TRY(plm_check_device(device));
     const size_t P = (size_t)L * (L - 1) / 2, qq = (size_t)q * q, LL = (size_t)L * L;
-    if ((rc = check_free(8.0 * ((double)P * qq + (double)LL * qq + (double)L * q) + L, "the double-mutant matrix")))
-        return rc;
+    PLM_TRY(plm_check_free(8.0 * ((double)P * qq + (double)LL * qq + (double)L * q) + L, "the double-mutant matrix"));
     hipStream_t st = (hipStream_t)stream;
     double *J = nullptr, *s = nullptr, *D = nullptr;
     int8_t *t = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {J, s, D, t};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    if ((rc = dmalloc(&J, P * qq)) || (rc = dmalloc(&s, (size_t)L * q)) || (rc = dmalloc(&D, LL * qq)) ||
-        (rc = dmalloc(&t, (size_t)L)))
-        return done(rc);
-    hipError_t e = upload_pairs(jij_full, L, q, J, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s, smm, sizeof(double) * L * q, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(t, target, (size_t)L, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return done(plm_fail(PLM_EDEVICE, "upload failed: %s", hipGetErrorString(e)));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&J, P * qq));
+    PLM_TRY(mem.alloc(&s, (size_t)L * q));
+    PLM_TRY(mem.alloc(&D, LL * qq));
+    PLM_TRY(mem.alloc(&t, (size_t)L));
+    PLM_TRY(upload_pairs(jij_full, L, q, J, st));
+    PLM_HIP(hipMemcpyAsync(s, smm, sizeof(double) * L * q, hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemcpyAsync(t, target, (size_t)L, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_double_mutants, dim3((unsigned)(P + L)), dim3(256), 0, st, J, s, t, L, q, D);
-    if ((e = hipGetLastError()) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "k_double_mutants launch failed"));
-    e = hipMemcpyAsync(dmm_out, D, sizeof(double) * LL * qq, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return done(e == hipSuccess ? PLM_OK : plm_fail(PLM_EDEVICE, "double mutants failed: %s", hipGetErrorString(e)));
+    PLM_HIP(hipGetLastError());
+    PLM_HIP(hipMemcpyAsync(dmm_out, D, sizeof(double) * LL * qq, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
+    return PLM_OK;
 }
 
 int plm_independent_fields(const double *fi, int32_t n_sites, int32_t n_states, double lambda_h, double n_eff,
@@ -302,38 +268,27 @@ int plm_independent_fields(const double *fi, int32_t n_sites, int32_t n_states, 
         return plm_fail(PLM_EUNSUPPORTED, "independent fields support 2..32 states (got %d)", n_states);
     if (!(lambda_h > 0.0)) return plm_fail(PLM_EINVAL, "lambda_h must be > 0 (got %g): the optimum need not exist", lambda_h);
     if (!(n_eff >= 0.0) || !isfinite(n_eff)) return plm_fail(PLM_EINVAL, "N_eff must be finite and >= 0 (got %g)", n_eff);
-    int rc = plm_check_device(device);
-    if (rc) return rc;
+    PLM_TRY(plm_check_device(device));
     const int L = n_sites, q = n_states;
-    if ((rc = check_free(8.0 * 2.0 * L * q + 4.0 * L, "independent fields"))) return rc;
+    PLM_TRY(plm_check_free(8.0 * 2.0 * L * q + 4.0 * L, "independent fields"));
     hipStream_t st = (hipStream_t)stream;
     double *f = nullptr, *h = nullptr;
     int32_t *it = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {f, h, it};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-    if ((rc = dmalloc(&f, (size_t)L * q)) || (rc = dmalloc(&h, (size_t)L * q)) || (rc = dmalloc(&it, (size_t)L)))
-        return done(rc);
-    hipError_t e = hipMemcpyAsync(f, fi, sizeof(double) * L * q, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return done(plm_fail(PLM_EDEVICE, "upload failed: %s", hipGetErrorString(e)));
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&f, (size_t)L * q));
+    PLM_TRY(mem.alloc(&h, (size_t)L * q));
+    PLM_TRY(mem.alloc(&it, (size_t)L));
+    PLM_HIP(hipMemcpyAsync(f, fi, sizeof(double) * L * q, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_independent_fields, dim3(L), dim3(64), 0, st, f, L, q, lambda_h, n_eff, h, it);
-    if ((e = hipGetLastError()) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "k_independent_fields launch failed"));
-    int32_t *iters = iters_out;
-    int32_t *own = nullptr;
-    if (!iters) iters = own = new int32_t[L];
-    e = hipMemcpyAsync(h_out, h, sizeof(double) * L * q, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(iters, it, sizeof(int32_t) * L, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    int bad = -1;
-    for (int k = 0; e == hipSuccess && k < L && bad < 0; k++)
-        if (iters[k] < 0) bad = k;
-    delete[] own;
-    if (e != hipSuccess) return done(plm_fail(PLM_EDEVICE, "independent fields failed: %s", hipGetErrorString(e)));
-    if (bad >= 0)
-        return done(plm_fail(PLM_ENUMERIC, "independent-site Newton solve of site %d did not reach |g| <= 1e-12 max(1, N_eff) "
-                                           "in %d steps", bad, MA_NEWTON_CAP));
-    return done(PLM_OK);
+    PLM_HIP(hipGetLastError());
+    std::vector<int32_t> own(iters_out ? 0 : L);
+    int32_t *iters = iters_out ? iters_out : own.data();
+    PLM_HIP(hipMemcpyAsync(h_out, h, sizeof(double) * L * q, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipMemcpyAsync(iters, it, sizeof(int32_t) * L, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < L; k++)
+        if (iters[k] < 0)
+            return plm_fail(PLM_ENUMERIC, "independent-site Newton solve of site %d did not reach |g| <= 1e-12 max(1, N_eff) "
+                                          "in %d steps", k, MA_NEWTON_CAP);
+    return PLM_OK;
 }

@@ -9,7 +9,6 @@
 //                    walks sweeps x sites itself; W rows reach the lanes through LDS in chunks of j
 //   k_gibbs_direct   the other form: lanes = (chain, state), W rows read straight from global memory
 //   k_field_energy   (H, H_J, H_h) of the field-only model (L = 1), which the forward GEMM of plm_hamiltonians cannot take
-#include "../../include/plm_hip.h"
 #include "plm_sample_internal.h"
 #include "plm_gibbs_device.h"
 #include <hip/hip_runtime.h>
@@ -18,9 +17,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-
-int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
-int plm_check_device(int device);               // plm_host.cpp: visible gfx950 device, made current
 
 namespace {
 
@@ -210,6 +206,17 @@ __global__ void k_field_energy(const float *__restrict__ h, const int8_t *__rest
 
 typedef gibbs::SweepPlan Plan;
 
+const int TILES[3] = {64, 128, 256};            // chains per workgroup of the tiled form
+const int CHUNKS[6] = {1, 2, 4, 8, 12, 16};     // sites j per staged chunk
+
+// the row of a plan: float4 per q states, and the odd number of float4 the row takes in LDS
+Plan plan_rows(int q) {
+    Plan p = {};
+    p.NV = (q + 3) / 4;
+    p.NVP = (p.NV % 2 == 0) ? p.NV + 1 : p.NV;
+    return p;
+}
+
 // The planner's own checks of one (tile, j-chunk): a chunk is at most GS_PF float4 per thread, and the two staging
 // buffers and the chain states fit the LDS of a CU.  Nothing that fails them is ever launched.
 bool tiled_fits(int L, int q, int tile, int JC, Plan *p) {
@@ -226,16 +233,12 @@ bool tiled_fits(int L, int q, int tile, int JC, Plan *p) {
 // by what the chain states leave of the LDS.  force_tile / force_jc != 0 (PLM_SAMPLE_TILE / PLM_SAMPLE_JC) replace the
 // two preferences -- the spread over the CUs, and no chunk of 2 L sites or more -- and none of the checks.
 bool make_plan(int L, int q, int C, int n_cu, int force_tile, int force_jc, Plan *out) {
-    Plan p = {};
-    p.NV = (q + 3) / 4;
-    p.NVP = (p.NV % 2 == 0) ? p.NV + 1 : p.NV;
-    const int tiles[3] = {256, 128, 64};
-    const int cands[6] = {16, 12, 8, 4, 2, 1};
-    for (int t = 0; t < 3; t++) {
-        const int tile = tiles[t];
-        if (force_tile ? tile != force_tile : (t < 2 && (C + tile - 1) / tile < n_cu)) continue;   // spread small calls over the CUs
-        for (int c = 0; c < 6; c++) {
-            const int JC = cands[c];
+    Plan p = plan_rows(q);
+    for (int t = 2; t >= 0; t--) {
+        const int tile = TILES[t];
+        if (force_tile ? tile != force_tile : (tile > 64 && (C + tile - 1) / tile < n_cu)) continue;   // spread small calls over the CUs
+        for (int c = 5; c >= 0; c--) {
+            const int JC = CHUNKS[c];
             if (force_jc ? JC != force_jc : (JC > 1 && JC >= 2 * L)) continue;
             if (tiled_fits(L, q, tile, JC, &p)) {
                 *out = p;
@@ -246,55 +249,6 @@ bool make_plan(int L, int q, int C, int n_cu, int force_tile, int force_jc, Plan
     return false;       // tile 64 with JC = 1 is the smallest plan there is: no other tile or chunk fits either
 }
 
-template <int NV, int TILE>
-hipError_t launch_gibbs_t(const Plan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
-                          const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
-                          int8_t *dst) {
-    auto kern = k_gibbs<NV, TILE>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((C + TILE - 1) / TILE)), dim3(TILE), p.lds, st, W, L, q, C, p.JC, src, fixed,
-                       allowed, beta, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), sweep0, n_sweeps, dst);
-    return hipGetLastError();
-}
-
-template <int NV>
-hipError_t launch_gibbs_nv(const Plan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
-                           const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
-                           int8_t *dst) {
-    switch (p.tile) {
-    case 256: return launch_gibbs_t<NV, 256>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    case 128: return launch_gibbs_t<NV, 128>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    default: return launch_gibbs_t<NV, 64>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    }
-}
-
-hipError_t launch_gibbs(const Plan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
-                        const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
-                        int8_t *dst) {
-#define GS_CASE(n) \
-    case n: return launch_gibbs_nv<n>(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    switch (p.NV) {
-        GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE(8)
-    }
-#undef GS_CASE
-    return hipErrorInvalidValue;
-}
-
-template <int QP>
-hipError_t launch_direct_t(hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src, const uint8_t *fixed,
-                           uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps, int8_t *dst) {
-    constexpr int CPW = 256 / QP;
-    const size_t lds = (size_t)CPW * ((L + 3) / 4 * 4);     // direct_lds(L, q): QP = direct_group(L, q)
-    auto kern = k_gibbs_direct<QP>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((C + CPW - 1) / CPW)), dim3(256), lds, st, (const float *)W, L, q,
-                       (q + 3) / 4 * 4, C, src, fixed, allowed, beta, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
-                       sweep0, n_sweeps, dst);
-    return hipGetLastError();
-}
-
 // lanes per chain of the direct form: the power of two >= q, and a larger one (fewer chains per workgroup, the lanes
 // a >= q idle) where the states of that many chains would not fit the LDS
 int direct_group(int L, int q) {
@@ -303,18 +257,6 @@ int direct_group(int L, int q) {
     return g;
 }
 size_t direct_lds(int L, int q) { return (size_t)(256 / direct_group(L, q)) * ((L + 3) / 4 * 4); }
-bool direct_fits(int L, int q) { return direct_lds(L, q) <= GS_LDS_BYTES; }
-
-hipError_t launch_direct(hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src, const uint8_t *fixed,
-                         uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps, int8_t *dst) {
-    switch (direct_group(L, q)) {
-    case 2: return launch_direct_t<2>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    case 4: return launch_direct_t<4>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    case 8: return launch_direct_t<8>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    case 16: return launch_direct_t<16>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    default: return launch_direct_t<32>(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    }
-}
 
 // 0: the variable is not set; -1: it is set to something else than one of the values
 int env_choice(const char *name, const int *values, int n) {
@@ -328,10 +270,10 @@ int env_choice(const char *name, const int *values, int n) {
     return -1;
 }
 
-// The one place a plan is made: plm_sample and plm_bm_fit (through gibbs::plan_sweeps) and plm_sample_plan.  Host code.
+// The one place a plan is made: plm_sample, plm_ais and plm_bm_fit (through gibbs::plan_sweeps) and plm_sample_plan.
+// Host code.
 int choose_plan(int L, int q, int C, int n_cu, Plan *out) {
-    static const int tiles[3] = {64, 128, 256}, chunks[6] = {1, 2, 4, 8, 12, 16};
-    const int force_tile = env_choice("PLM_SAMPLE_TILE", tiles, 3), force_jc = env_choice("PLM_SAMPLE_JC", chunks, 6);
+    const int force_tile = env_choice("PLM_SAMPLE_TILE", TILES, 3), force_jc = env_choice("PLM_SAMPLE_JC", CHUNKS, 6);
     if (force_tile < 0) return plm_fail(PLM_EINVAL, "PLM_SAMPLE_TILE must be 64, 128 or 256 (got '%s')", getenv("PLM_SAMPLE_TILE"));
     if (force_jc < 0) return plm_fail(PLM_EINVAL, "PLM_SAMPLE_JC must be 1, 2, 4, 8, 12 or 16 (got '%s')", getenv("PLM_SAMPLE_JC"));
     // the tiled form wherever the chain states fit the LDS; the direct form for longer models, or on request
@@ -351,11 +293,9 @@ int choose_plan(int L, int q, int C, int n_cu, Plan *out) {
         direct = true;
     }
     if (direct) {
-        if (!direct_fits(L, q))
+        if (direct_lds(L, q) > GS_LDS_BYTES)
             return plm_fail(PLM_EUNSUPPORTED, "%d sites with %d states: the chain states of a workgroup do not fit the LDS of a CU", L, q);
-        plan = Plan{};
-        plan.NV = (q + 3) / 4;
-        plan.NVP = (plan.NV % 2 == 0) ? plan.NV + 1 : plan.NV;
+        plan = plan_rows(q);
         plan.tile = 256 / direct_group(L, q);      // chains per workgroup
         plan.lds = direct_lds(L, q);
     }
@@ -368,26 +308,59 @@ int choose_plan(int L, int q, int C, int n_cu, Plan *out) {
 
 namespace gibbs {
 
+int check_states(int q, const char *who) {
+    if (q < 2 || q > GS_Q) return plm_fail(PLM_EUNSUPPORTED, "%s supports 2..32 states (got %d)", who, q);
+    return PLM_OK;
+}
+
+int check_chain_sites(int C, int L) {
+    if ((double)C * L >= 2147483647.0) return plm_fail(PLM_EINVAL, "n_chains x n_sites must stay below 2^31");
+    return PLM_OK;
+}
+
+double table_bytes(int L, int q) { return 16.0 * ((double)L * L * q + (double)L) * plan_rows(q).NV; }
+double canon_bytes(int L, int q) { return 4.0 * plm_n_canon(L, q); }
+
+int check_start(const int8_t *start, int C, int L, int q, uint32_t allowed, const uint8_t *fixed) {
+    for (size_t k = 0; k < (size_t)C * L; k++) {
+        const int v = start[k];
+        const int site = (int)(k % (size_t)L);
+        if (v < 0 || v >= q) return plm_fail(PLM_EINVAL, "start[%zu] = %d outside 0..%d", k, v, q - 1);
+        if (!((allowed >> v) & 1u) && !(fixed && fixed[site]))
+            return plm_fail(PLM_EINVAL, "start[%zu] = %d is not an allowed state and site %d is not fixed", k, v, site);
+    }
+    return PLM_OK;
+}
+
 int plan_sweeps(int L, int q, int C, int device, SweepPlan *out) {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDeviceProperties failed");
+    PLM_HIP(hipGetDeviceProperties(&prop, device));
     return choose_plan(L, q, C, prop.multiProcessorCount, out);
 }
 
-size_t table_float4(int L, int q) { return ((size_t)L * L * q + (size_t)L) * ((q + 3) / 4); }
+size_t table_float4(int L, int q) { return ((size_t)L * L * q + (size_t)L) * plan_rows(q).NV; }
 
 hipError_t expand(hipStream_t st, const float *canon, int L, int q, float4 *W) {
-    const size_t n_w4 = table_float4(L, q);
-    hipLaunchKernelGGL(k_sample_expand, dim3((unsigned)((n_w4 + 255) / 256)), dim3(256), 0, st, canon, L, q,
-                       (q + 3) / 4 * 4, W);
+    hipLaunchKernelGGL(k_sample_expand, dim3((unsigned)((table_float4(L, q) + 255) / 256)), dim3(256), 0, st, canon, L, q,
+                       plan_rows(q).NV * 4, W);
     return hipGetLastError();
 }
 
 hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
                   const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
                   int8_t *dst) {
-    if (p.direct) return launch_direct(st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
-    return launch_gibbs(p, st, W, L, q, C, src, fixed, allowed, beta, seed, sweep0, n_sweeps, dst);
+    const uint32_t seed_lo = (uint32_t)(seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(seed >> 32);
+    return dispatch(
+        p,
+        [&](auto nv, auto tile) {
+            return launch(k_gibbs<nv(), tile()>, (unsigned)((C + tile() - 1) / tile()), tile(), p, st, W, L, q, C, p.JC, src,
+                          fixed, allowed, beta, seed_lo, seed_hi, sweep0, n_sweeps, dst);
+        },
+        [&](auto qp) {
+            const int cpw = 256 / qp();              // chains per workgroup
+            return launch(k_gibbs_direct<qp()>, (unsigned)((C + cpw - 1) / cpw), 256, p, st, (const float *)W, L, q,
+                          p.NV * 4, C, src, fixed, allowed, beta, seed_lo, seed_hi, sweep0, n_sweeps, dst);
+        });
 }
 
 }  // namespace gibbs
@@ -396,15 +369,14 @@ int plm_sample_plan(int32_t n_sites, int32_t n_states, int32_t n_chains, int32_t
     if (!out) return plm_fail(PLM_EINVAL, "NULL plan");
     if (n_sites < 1 || n_chains < 1)
         return plm_fail(PLM_EINVAL, "need n_sites >= 1 and n_chains >= 1 (got %d, %d)", n_sites, n_chains);
-    if (n_states < 2 || n_states > GS_Q)
-        return plm_fail(PLM_EUNSUPPORTED, "the sampler supports 2..32 states (got %d)", n_states);
+    int rc = gibbs::check_states(n_states, "the sampler");
+    if (rc) return rc;
     Plan plan;
-    int rc;
     if (n_cu > 0) {
         rc = choose_plan(n_sites, n_states, n_chains, n_cu, &plan);      // no device, no HIP call
     } else {
         int device = 0;
-        if (hipGetDevice(&device) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipGetDevice failed");
+        PLM_HIP(hipGetDevice(&device));
         rc = gibbs::plan_sweeps(n_sites, n_states, n_chains, device, &plan);
     }
     if (rc) return rc;
@@ -424,30 +396,21 @@ int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
     if (L < 1 || C < 1 || K < 1 || opts->burn_in < 0 || (K > 1 && opts->thin < 1))
         return plm_fail(PLM_EINVAL, "need n_sites >= 1, n_chains >= 1, n_snapshots >= 1, burn_in >= 0, thin >= 1 "
                                     "(got %d, %d, %d, %d, %d)", L, C, K, opts->burn_in, opts->thin);
-    if (q < 2 || q > GS_Q) return plm_fail(PLM_EUNSUPPORTED, "the sampler supports 2..32 states (got %d)", q);
+    PLM_TRY(gibbs::check_states(q, "the sampler"));
     if (!(opts->beta > 0.f) || !isfinite(opts->beta))
         return plm_fail(PLM_EINVAL, "beta must be finite and > 0 (got %g)", (double)opts->beta);
     const int thin = K > 1 ? opts->thin : 0;
     if ((double)opts->burn_in + (double)(K - 1) * thin >= 4294967295.0)
         return plm_fail(PLM_EINVAL, "burn_in + (n_snapshots - 1) thin must stay below 2^32 - 1 sweeps");
-    int rc = plm_check_device(device);
-    if (rc) return rc;
+    PLM_TRY(plm_check_device(device));
     // sizes first: nothing below this point is dereferenced before the device is known to hold the call
-    const int QS = (q + 3) / 4 * 4;
-    const double table_b = 4.0 * ((double)L * L * q * QS + (double)L * QS);
-    const double canon_b = 4.0 * ((double)L * q + (double)L * (L - 1) / 2 * q * q);
+    const double table_b = gibbs::table_bytes(L, q);
     const double state_b = (double)C * L * ((double)K + 1.0) + L;
     const double energy_b = energies_out ? 24.0 * C : 0.0;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return plm_fail(PLM_EDEVICE, "hipMemGetInfo failed");
-    if (table_b + canon_b + state_b + energy_b > (double)free_b)
-        return plm_fail(PLM_ENOMEM, "the sampler needs %.2f GB of device memory (%.2f GB of it the expanded couplings), "
-                                    "%.2f GB are free (of %.1f GB)", (table_b + canon_b + state_b + energy_b) / 1e9,
-                        table_b / 1e9, free_b / 1e9, total_b / 1e9);
-    if ((double)C * L * K >= 9.0e18 || (double)C * L >= 2147483647.0)
-        return plm_fail(PLM_EINVAL, "n_chains x n_sites must stay below 2^31");
+    PLM_TRY(plm_check_free(table_b + gibbs::canon_bytes(L, q) + state_b + energy_b, "the sampler", table_b));
+    PLM_TRY(gibbs::check_chain_sites(C, L));
     if (!x_canonical || !samples_out) return plm_fail(PLM_EINVAL, "NULL argument");
-    uint32_t allowed = q == 32 ? 0xFFFFFFFFu : ((1u << q) - 1u);
+    uint32_t allowed = plm_state_mask(q);
     if (opts->allowed) {
         uint32_t m = 0;
         for (int a = 0; a < q; a++)
@@ -455,81 +418,49 @@ int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
         if (!m) return plm_fail(PLM_EINVAL, "no state is allowed");
         allowed = m;
     }
-    if (opts->start)
-        for (size_t k = 0; k < (size_t)C * L; k++) {
-            const int v = opts->start[k];
-            const int site = (int)(k % (size_t)L);
-            if (v < 0 || v >= q) return plm_fail(PLM_EINVAL, "start[%zu] = %d outside 0..%d", k, v, q - 1);
-            if (!((allowed >> v) & 1u) && !(opts->fixed && opts->fixed[site]))
-                return plm_fail(PLM_EINVAL, "start[%zu] = %d is not an allowed state and site %d is not fixed", k, v, site);
-        }
+    if (opts->start) PLM_TRY(gibbs::check_start(opts->start, C, L, q, allowed, opts->fixed));
     Plan plan;
-    rc = gibbs::plan_sweeps(L, q, C, device, &plan);
-    if (rc) return rc;
-    const bool direct = plan.direct;
+    PLM_TRY(gibbs::plan_sweeps(L, q, C, device, &plan));
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_canon = (size_t)L * q + (size_t)L * (L - 1) / 2 * q * q;
-    const size_t n_w4 = ((size_t)L * L * q + (size_t)L) * (QS / 4);
-    const size_t CL = (size_t)C * L;
+    const size_t n_canon = (size_t)plm_n_canon(L, q), CL = (size_t)C * L;
     float *canon = nullptr;
     float4 *W = nullptr;
     int8_t *start = nullptr, *snaps = nullptr;
     uint8_t *fixed = nullptr;
     double *en = nullptr;
-    auto done = [&](int code) {
-        void *all[] = {canon, W, start, snaps, fixed, en};
-        for (void *b : all)
-            if (b) (void)hipFree(b);
-        return code;
-    };
-#define GS_ALLOC(ptr, bytes)                                                                   \
-    if (hipMalloc((void **)&ptr, std::max<size_t>((bytes), 16)) != hipSuccess) {               \
-        ptr = nullptr;                                                                         \
-        return done(plm_fail(PLM_ENOMEM, "hipMalloc of %zu bytes failed", (size_t)(bytes)));   \
-    }
-    GS_ALLOC(canon, n_canon * sizeof(float));
-    GS_ALLOC(W, n_w4 * sizeof(float4));
-    GS_ALLOC(snaps, CL * (size_t)K);
-    if (opts->start) GS_ALLOC(start, CL);
-    if (opts->fixed) GS_ALLOC(fixed, (size_t)L);
-    if (energies_out && L == 1) GS_ALLOC(en, CL * (size_t)K * 3 * sizeof(double));
-#undef GS_ALLOC
-    hipError_t e;
-#define ET(expr)              \
-    if ((e = (expr)) != hipSuccess) return done(plm_fail(PLM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));
-    ET(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
-    if (start) ET(hipMemcpyAsync(start, opts->start, CL, hipMemcpyHostToDevice, st));
-    if (fixed) ET(hipMemcpyAsync(fixed, opts->fixed, (size_t)L, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_sample_expand, dim3((unsigned)((n_w4 + 255) / 256)), dim3(256), 0, st, canon, L, q, QS, W);
-    ET(hipGetLastError());
+    DeviceBuffers mem;
+    PLM_TRY(mem.alloc(&canon, n_canon));
+    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(mem.alloc(&snaps, CL * (size_t)K));
+    if (opts->start) PLM_TRY(mem.alloc(&start, CL));
+    if (opts->fixed) PLM_TRY(mem.alloc(&fixed, (size_t)L));
+    if (energies_out && L == 1) PLM_TRY(mem.alloc(&en, CL * (size_t)K * 3));
+    PLM_HIP(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    if (start) PLM_HIP(hipMemcpyAsync(start, opts->start, CL, hipMemcpyHostToDevice, st));
+    if (fixed) PLM_HIP(hipMemcpyAsync(fixed, opts->fixed, (size_t)L, hipMemcpyHostToDevice, st));
+    PLM_HIP(gibbs::expand(st, canon, L, q, W));
     for (int k = 0; k < K; k++) {
         const int8_t *src = k == 0 ? start : snaps + (size_t)(k - 1) * CL;
         const uint32_t sweep0 = k == 0 ? 0u : (uint32_t)opts->burn_in + (uint32_t)(k - 1) * (uint32_t)thin;
-        const int n_sweeps = k == 0 ? opts->burn_in : thin;
-        if (direct) {
-            ET(launch_direct(st, W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0, n_sweeps,
-                             snaps + (size_t)k * CL));
-        } else {
-            ET(launch_gibbs(plan, st, W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0, n_sweeps,
-                            snaps + (size_t)k * CL));
-        }
+        PLM_HIP(gibbs::sweeps(plan, st, W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0,
+                              k == 0 ? opts->burn_in : thin, snaps + (size_t)k * CL));
     }
-    ET(hipMemcpyAsync(samples_out, snaps, CL * (size_t)K, hipMemcpyDeviceToHost, st));
-    if (energies_out && L == 1) {
+    PLM_HIP(hipMemcpyAsync(samples_out, snaps, CL * (size_t)K, hipMemcpyDeviceToHost, st));
+    if (en) {
         const int64_t n = (int64_t)CL * K;
         hipLaunchKernelGGL(k_field_energy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, canon, snaps, n, en);
-        ET(hipGetLastError());
-        ET(hipMemcpyAsync(energies_out, en, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        PLM_HIP(hipGetLastError());
+        PLM_HIP(hipMemcpyAsync(energies_out, en, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    ET(hipStreamSynchronize(st));
-#undef ET
-    rc = done(PLM_OK);
+    PLM_HIP(hipStreamSynchronize(st));
+    mem.free_all();                          // before plm_hamiltonians allocates its own
+    int rc = PLM_OK;
     if (energies_out && L > 1) {
         // the statistical energies of the snapshots at beta = 1: the code path of plm_hamiltonians, in row chunks that
         // stay inside its limit on sequences per call
         const size_t Lp = ((size_t)L + 31) / 32 * 32;
         const size_t max_rows = std::max<size_t>(256, (((size_t)1 << 30) / Lp) / 256 * 256);
-        const size_t rows = CL / (size_t)L * (size_t)K;
+        const size_t rows = (size_t)C * (size_t)K;
         for (size_t r0 = 0; r0 < rows && rc == PLM_OK; r0 += max_rows) {
             const size_t n = std::min(max_rows, rows - r0);
             rc = plm_hamiltonians(samples_out + r0 * L, (int32_t)n, L, q, x_canonical, device, stream,

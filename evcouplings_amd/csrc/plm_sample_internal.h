@@ -1,16 +1,25 @@
-// plm_sample_internal.h -- what plm_sample.hip lends to plm_bm.hip: the expansion of the couplings and the sweep
-// launchers, with the choice between the tiled and the direct form that plm_sample makes.
+// plm_sample_internal.h -- what plm_sample.hip shares with plm_ais.hip and plm_bm.hip: the checks the three entry points
+// open with, the plan, the expansion of the couplings, the sweep launchers, and the step from a plan to the template
+// arguments of a sweep kernel.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "plm_host_util.h"
+#include <type_traits>
 
 namespace gibbs {
 
 struct SweepPlan {
     int NV, NVP, tile, JC;      // the tiled form: float4 per row, padded row, chains per workgroup, j-chunk
     size_t lds;
-    bool direct;                // the direct form instead
+    bool direct;                // the direct form instead (tile = chains per workgroup = 256 / lanes per chain)
 };
+
+// ---- the front matter of plm_sample, plm_ais and plm_bm_fit ----
+int check_states(int q, const char *who);             // 2..32 states, or PLM_EUNSUPPORTED
+int check_chain_sites(int C, int L);                  // n_chains x n_sites < 2^31, or PLM_EINVAL
+double table_bytes(int L, int q);                     // the expanded table
+double canon_bytes(int L, int q);                     // one float32 vector in the canonical layout
+// start [C][L]: every state in 0 .. q-1 and, unless its site is fixed (fixed may be NULL), allowed; or PLM_EINVAL
+int check_start(const int8_t *start, int C, int L, int q, uint32_t allowed, const uint8_t *fixed);
 
 // PLM_OK and the plan, or PLM_EDEVICE / PLM_EUNSUPPORTED / PLM_EINVAL (a PLM_SAMPLE_TILE or PLM_SAMPLE_JC without a
 // valid plan) with the message recorded
@@ -25,5 +34,50 @@ hipError_t expand(hipStream_t st, const float *canon, int L, int q, float4 *W);
 hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
                   const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
                   int8_t *dst);
+
+// ---- from a plan to a kernel ----
+template <int V> using Int = std::integral_constant<int, V>;
+
+template <int NV, typename F> hipError_t with_tile(int tile, F &f) {
+    switch (tile) {
+    case 64: return f(Int<NV>{}, Int<64>{});
+    case 128: return f(Int<NV>{}, Int<128>{});
+    case 256: return f(Int<NV>{}, Int<256>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// tiled(Int<NV>, Int<TILE>) for NV = 1 .. 8 and TILE = 64, 128, 256, or direct(Int<QP>) for QP = 2, 4, 8, 16, 32 lanes
+// per chain: every plan the planner makes is one of these (tests/test_sampler_plan_host.py)
+template <typename Tiled, typename Direct> hipError_t dispatch(const SweepPlan &p, Tiled tiled, Direct direct) {
+    if (p.direct) switch (256 / p.tile) {
+        case 2: return direct(Int<2>{});
+        case 4: return direct(Int<4>{});
+        case 8: return direct(Int<8>{});
+        case 16: return direct(Int<16>{});
+        case 32: return direct(Int<32>{});
+        default: return hipErrorInvalidValue;
+        }
+    switch (p.NV) {
+    case 1: return with_tile<1>(p.tile, tiled);
+    case 2: return with_tile<2>(p.tile, tiled);
+    case 3: return with_tile<3>(p.tile, tiled);
+    case 4: return with_tile<4>(p.tile, tiled);
+    case 5: return with_tile<5>(p.tile, tiled);
+    case 6: return with_tile<6>(p.tile, tiled);
+    case 7: return with_tile<7>(p.tile, tiled);
+    case 8: return with_tile<8>(p.tile, tiled);
+    }
+    return hipErrorInvalidValue;
+}
+
+// one launch with the plan's dynamic LDS
+template <typename... P, typename... A>
+hipError_t launch(void (*kern)(P...), unsigned grid, unsigned block, const SweepPlan &p, hipStream_t st, A... args) {
+    const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), p.lds, st, args...);
+    return hipGetLastError();
+}
 
 }  // namespace gibbs

@@ -297,6 +297,8 @@ int plm_independent_fields(const double *fi, int32_t n_sites, int32_t n_states, 
  * 20 480, the tiled form up to about 2 500 and the slower direct form beyond, see plm_sample_plan).  samples_out: K x C x L states; energies_out: K x C x 3 doubles (H, H_J, H_h) of the snapshots at beta = 1,
  * what plm_hamiltonians returns for those rows, or NULL.  PLM_ENOMEM before any allocation, and before any array is
  * read, when the device cannot hold the expanded couplings (L^2 q ceil4(q) floats), the chain states and the outputs.
+ * In plm_sample, plm_bm_fit and plm_ais an out-of-memory error that HIP reports only at a call after the allocations is
+ * PLM_ENOMEM too (it was PLM_EDEVICE), as in plm_ctx_create.
  * PLM_EINVAL: start states outside 0..q-1, or not allowed at a site that is not fixed; no allowed state; beta not
  * finite or <= 0. */
 typedef struct {

@@ -110,6 +110,29 @@ def test_every_plan_of_the_sweep_is_valid_and_the_one_made_before_the_hooks():
     assert min(seen.values()) > 0, seen
 
 
+def test_every_plan_names_an_instantiated_kernel():
+    """The dispatch of plm_sample_internal.h turns (direct, tile, nv) into template arguments and knows k_gibbs / k_ais
+    <NV 1..8, TILE 64 | 128 | 256> and k_gibbs_direct / k_ais_direct <QP 2 | 4 | 8 | 16 | 32> only: the planner must not
+    return anything else, for any alphabet, on either side of the hand-over from the tiled to the direct form (L = 2484 /
+    2485 at q = 21, up to 2556 / 2557 at q = 2) and at a length only the direct form serves."""
+    tiled = {(nv, tile) for nv in range(1, 9) for tile in (64, 128, 256)}
+    groups = {2, 4, 8, 16, 32}
+    seen = set()
+    for q, L, (C, n_cu) in itertools.product(QS, (1, 37, 300, 2416, 2484, 2485, 2556, 2557, 20480),
+                                             ((300, 256), (40000, 256), (65536, 64))):
+        p = plm.sample_plan(L, q, C, n_cu=n_cu)
+        where = (L, q, C, n_cu, p)
+        if p["direct"]:
+            assert 256 % p["tile"] == 0 and 256 // p["tile"] in groups and 256 // p["tile"] >= q, where
+        else:
+            assert (p["nv"], p["tile"]) in tiled, where
+        assert p["nv"] == _ceil(q, 4) and 0 < p["lds_bytes"] <= 163840, where
+        seen.add(p["direct"])
+        if L == 20480:
+            assert p["direct"], where
+    assert seen == {False, True}
+
+
 def test_documented_plans():
     """The plans DESIGN_NEXT_ROWS.md section 9.6 states, on 256 CUs."""
     big = plm.sample_plan(300, 21, 65536, n_cu=256)      # 76.8 KB of states + 75 KB of staging, k_gibbs<6, 256>
