@@ -107,6 +107,27 @@ class PlmAisResult(C.Structure):
 
 AIS_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
 
+
+
+class PlmPtOpts(C.Structure):
+    _fields_ = [
+        ("n_ladders", C.c_int32), ("n_rungs", C.c_int32), ("burn_in", C.c_int32), ("n_snapshots", C.c_int32),
+        ("thin", C.c_int32), ("sweeps_per_round", C.c_int32), ("first_round", C.c_int32), ("all_rungs", C.c_int32),
+        ("betas", C.c_void_p), ("seed", C.c_uint64),
+        ("start", C.c_void_p), ("start_rungs", C.c_void_p), ("start_e", C.c_void_p),
+    ]
+
+
+class PlmPtResult(C.Structure):
+    _fields_ = [
+        ("samples", C.c_void_p), ("e_j", C.c_void_p), ("accepts", C.c_void_p), ("attempts", C.c_void_p),
+        ("walkers", C.c_void_p), ("rungs", C.c_void_p), ("walker_e", C.c_void_p),
+        ("rounds_done", C.c_int32), ("status", C.c_int32),
+    ]
+
+
+PT_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -142,6 +163,8 @@ SYMBOLS = [
                              C.POINTER(PlmBmResult)]),
     ("plm_ais", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmAisOpts), C.c_int, _P, AIS_CB, _P,
                           C.POINTER(PlmAisResult)]),
+    ("plm_pt", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmPtOpts), C.c_int, _P, PT_CB, _P,
+                         C.POINTER(PlmPtResult)]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),

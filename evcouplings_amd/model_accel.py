@@ -118,6 +118,59 @@ def sample_sequences(model, n_chains, burn_in=100, n_snapshots=1, thin=1, beta=1
     return (res, en.reshape(-1, 3)) if energies else res
 
 
+def sample_tempered(model, n_ladders, betas=None, n_rungs=8, beta_max=1.0, burn_in=100, n_snapshots=1, thin=1,
+                    sweeps_per_round=1, seed=0, start=None, as_letters=True, energies=False, info=False, device=0):
+    """
+    Draw sequences of a `CouplingsModel` (as for `sample_sequences`) by parallel tempering (`plm.parallel_tempering`,
+    DESIGN_NEXT_ROWS.md section 9.9): n_ladders independent ladders whose walkers exchange between the inverse
+    temperatures `betas` on the couplings (None: `plm.tempering_ladder(n_rungs, beta_max)`), burn_in rounds, then
+    n_snapshots snapshots thin rounds apart of the walker at the top rung.  With beta_max = 1 these are samples of the
+    model itself, as `sample_sequences` draws at beta = 1, from chains that cross between its modes through the upper
+    rungs.  All states are allowed at all sites.
+      start    None (the sampler's start rule), "target" (every walker starts from the target sequence), or an
+               (n_ladders * R, L) matrix of letters or of states
+    Returns an (n_snapshots * n_ladders, L) matrix of letters (as_letters) or of int8 states, snapshots one after the
+    other; with energies=True followed by the (n_snapshots * n_ladders, 3) energies (H, H_J, H_h) at beta = 1; with
+    info=True followed by the dict of `plm.parallel_tempering` (acceptance rates, walkers for a continuation).
+    """
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    letters, code = _letters_and_code(model, q)
+    if betas is None:
+        betas = plm.tempering_ladder(n_rungs, beta_max)
+    betas = np.asarray(betas, np.float32).reshape(-1)
+
+    def states(mat):
+        mat = np.asarray(mat)
+        if mat.dtype.kind in "iu":
+            return mat.astype(np.int8)
+        try:
+            return np.vectorize(code.__getitem__, otypes=[np.int8])(mat.astype("U1"))
+        except KeyError as e:
+            raise ValueError("letter %s is not in the model's alphabet" % e)
+
+    n_walkers = int(n_ladders) * betas.size
+    if isinstance(start, str):
+        if start != "target":
+            raise ValueError('start must be None, "target" or a matrix')
+        x0 = (np.tile(states(np.array(list(model.target_seq))), (n_walkers, 1)),)
+    elif start is not None:
+        x0 = (states(start).reshape(n_walkers, L).copy(),)
+    else:
+        x0 = None
+    res = plm.parallel_tempering(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_ladders, betas, burn_in=burn_in,
+                                 n_snapshots=n_snapshots, thin=thin, sweeps_per_round=sweeps_per_round, seed=seed,
+                                 start=x0, device=device)
+    out = np.asarray(res["samples"]).reshape(-1, L)
+    ret = (letters[out.astype(np.int64)] if as_letters else out,)
+    if energies:
+        ret += (np.asarray(res["energies"]).reshape(-1, 3),)
+    if info:
+        ret += (res,)
+    return ret if len(ret) > 1 else ret[0]
+
+
 def _letters_and_code(model, q):
     letters = np.array(list(model.alphabet) if isinstance(model.alphabet, str) else model.alphabet).astype("U1")
     if len(letters) != q:

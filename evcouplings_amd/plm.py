@@ -281,6 +281,159 @@ def log_partition(hi, jij, q, n_chains=4096, n_temps=1000, sweeps_per_temp=1, be
     return out
 
 
+def tempering_ladder(n_rungs, beta_max=1.0, kind="linear"):
+    """
+    A ladder of n_rungs inverse temperatures for `parallel_tempering`, float32, from beta_0 = 0 to beta_max.
+    kind = "linear": beta_r = beta_max r / (R - 1).  kind = "geometric": beta_0 = 0 and the other rungs in geometric
+    progression up to beta_max with the ratio 2 (beta_r = beta_max 2^(r - R + 1)): close rungs where the couplings are
+    weak, wide ones near beta_max.  One rung is beta_max alone.
+    """
+    R, top = int(n_rungs), float(beta_max)
+    if R < 1 or not (top >= 0.0 and np.isfinite(top)):
+        raise ValueError("need n_rungs >= 1 and a finite beta_max >= 0")
+    if R == 1:
+        return np.array([top], np.float32)
+    if kind == "linear":
+        return np.array([top * r / (R - 1) for r in range(R)], np.float32)
+    if kind == "geometric":
+        return np.array([0.0] + [top * 2.0 ** (r - R + 1) for r in range(1, R)], np.float32)
+    raise ValueError('kind must be "linear" or "geometric"')
+
+
+def parallel_tempering(hi, jij, q, n_ladders, betas, burn_in=10, n_snapshots=1, thin=1, sweeps_per_round=1, seed=0,
+                       all_rungs=False, start=None, first_round=0, callback=None, device=0):
+    """
+    Replica-exchange Gibbs sampling of the Potts model (hi, jij) on the GPU (plm_pt, DESIGN_NEXT_ROWS.md section 9.9):
+    n_ladders independent ladders of R = len(betas) walkers sample p_beta(x) ~ exp(sum_i h_i(x_i) + beta sum_{i<j}
+    J_ij(x_i, x_j)) at the inverse temperatures 0 <= beta_0 <= ... <= beta_{R-1} (see `tempering_ladder`).  A round is
+    sweeps_per_round Gibbs sweeps of every walker at the beta of its rung and one exchange pass between neighbouring rungs
+    (pairs (0,1), (2,3), .. in even rounds, (1,2), (3,4), .. in odd ones).  burn_in rounds, then n_snapshots snapshots
+    thin rounds apart.
+    start: None, or the `walkers` triple (states, rungs, e_j) of an earlier call, which this call then continues bit for
+    bit when first_round is the number of rounds made so far; (states, rungs) or (states, rungs, None) has the energies
+    measured, and rungs None puts slot s of every ladder at rung s.  callback(rounds_done, n_rounds) is called between
+    rounds and stops the run by returning a true value.
+    Returns a dict: samples int8 [K, C, L] (the walkers at the top rung) or, with all_rungs, [K, C, R, L] in rung order;
+    energies float64 [..., 3] = (H, H_J, H_h) of those rows at beta = 1, what `hamiltonians` gives; e_j [...] the tracked
+    coupling energy of those rows; accepts, attempts int64 [R - 1] and acceptance = accepts / attempts per pair of rungs;
+    walkers = (states int8 [C R, L], rungs int32 [C R], e_j float64 [C R]); rounds_done; status ("converged" or
+    "interrupted": snapshots not yet taken are zero then).
+    """
+    q, C_, K = int(q), int(n_ladders), int(n_snapshots)
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
+        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
+    L = hi.shape[0]
+    jij = np.ascontiguousarray(jij, dtype=np.float32)
+    if jij.size != L * (L - 1) // 2 * q * q:
+        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
+    R = betas.size
+    if R < 1:
+        raise ValueError("betas must hold at least one inverse temperature")
+    x0 = rungs0 = e0 = None
+    if start is not None:
+        parts = tuple(start) + (None,) * (3 - len(start)) if 1 <= len(start) <= 3 else ()
+        if len(parts) != 3 or parts[0] is None:
+            raise ValueError("start must be (states, rungs, e_j), (states, rungs) or (states,)")
+        x0 = np.ascontiguousarray(parts[0], dtype=np.int8)
+        if x0.shape != (max(C_, 0) * R, L):
+            raise ValueError("the start states must be an (n_ladders * R, L) = (%d, %d) matrix" % (C_ * R, L))
+        if parts[1] is not None:
+            rungs0 = np.ascontiguousarray(parts[1], dtype=np.int32).reshape(-1)
+            if rungs0.size != C_ * R:
+                raise ValueError("the start rungs must hold n_ladders * R = %d values" % (C_ * R))
+        if parts[2] is not None:
+            if rungs0 is None:
+                raise ValueError("start energies need the start rungs")
+            e0 = np.ascontiguousarray(parts[2], dtype=np.float64).reshape(-1)
+            if e0.size != C_ * R:
+                raise ValueError("the start energies must hold n_ladders * R = %d values" % (C_ * R))
+    lib = _lib.load()
+    opts = _lib.PlmPtOpts(C_, R, int(burn_in), K, int(thin), int(sweeps_per_round), int(first_round),
+                          1 if all_rungs else 0, _ptr(betas), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(x0), _ptr(rungs0),
+                          _ptr(e0))
+    Cn, Kn = max(C_, 1), max(K, 1)
+    shape = (Kn, Cn, R) if all_rungs else (Kn, Cn)
+    samples, e_j = np.zeros(shape + (L,), np.int8), np.zeros(shape)
+    accepts, attempts = np.zeros(R - 1, np.int64), np.zeros(R - 1, np.int64)
+    walkers, rungs, walker_e = np.zeros((Cn * R, L), np.int8), np.zeros(Cn * R, np.int32), np.zeros(Cn * R)
+    res = _lib.PlmPtResult(_ptr(samples), _ptr(e_j), _ptr(accepts) if R > 1 else None,
+                           _ptr(attempts) if R > 1 else None, _ptr(walkers), _ptr(rungs), _ptr(walker_e), 0, 0)
+    failure = []
+
+    def _cb(done, total, _user):
+        try:
+            return 1 if callback(int(done), int(total)) else 0
+        except BaseException as exc:     # an exception must not cross the C frames
+            failure.append(exc)
+            return 1
+
+    cb = _lib.PT_CB(_cb) if callback is not None else _lib.PT_CB()
+    check(lib.plm_pt(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb, None, C.byref(res)))
+    if failure:
+        raise failure[0]
+    rows = samples.reshape(-1, L)
+    if L > 1:
+        en = hamiltonians(rows, q, hi, jij, device=device)
+    else:
+        hh = hi[0].astype(np.float64)[rows[:, 0]]
+        en = np.stack([hh, np.zeros_like(hh), hh], axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        acceptance = accepts / attempts.astype(np.float64)
+    return dict(samples=samples, energies=en.reshape(shape + (3,)), e_j=e_j, accepts=accepts, attempts=attempts,
+                acceptance=acceptance, walkers=(walkers, rungs, walker_e), rounds_done=int(res.rounds_done),
+                status=BM_STATUS[int(res.status)])
+
+
+def tempered_log_z(e_j, betas, log_z0):
+    """
+    The estimate of `log_partition_tempered` from the tracked energies e_j [K, C, R] of all rungs: (log_z, log_z_se,
+    se of every step [R - 1]), all in float64.  Step r: m_r + log mean exp(d_r E_r - m_r) over the snapshots and ladders of
+    rung r, d_r = beta_{r+1} - beta_r, m_r = max d_r E_r; its standard error from the spread of the per-ladder means.
+    """
+    e_j = np.asarray(e_j, np.float64)
+    b = np.asarray(betas, np.float32).astype(np.float64)
+    K, Cn, R = e_j.shape
+    log_z, se = float(log_z0), np.zeros(max(R - 1, 0))
+    for r in range(R - 1):
+        a = (b[r + 1] - b[r]) * e_j[:, :, r]
+        m = a.max()
+        w = np.exp(a - m).mean(axis=0)              # one mean per ladder: ladders are independent, snapshots are not
+        log_z += m + np.log(w.mean())
+        se[r] = w.std(ddof=1) / (np.sqrt(Cn) * w.mean()) if Cn > 1 else 0.0
+    return log_z, float(np.sqrt((se * se).sum())), se
+
+
+def log_partition_tempered(hi, jij, q, n_ladders, betas, **kw):
+    """
+    log Z of the Potts model (hi, jij) with the couplings scaled by betas[-1], from one run of `parallel_tempering` (whose
+    keyword arguments these are; all_rungs is set) on a ladder that starts at beta_0 = 0, where log Z_0 = sum_i log sum_a
+    exp h_i(a) is known:
+        log_z = log Z_0 + sum_r [m_r + log mean exp((beta_{r+1} - beta_r) E_r - m_r)],
+    the mean over the snapshots and ladders of rung r, in float64.  log_z_se = sqrt(sum_r se_r^2), se_r the standard error
+    of step r from the per-ladder means (ladders are independent, snapshots of one ladder are not).  The correlation
+    between the rungs of a ladder is ignored in log_z_se; sum(se_rungs) bounds the error whatever that correlation is.
+    Unlike annealed importance sampling the estimate rests on equilibrium samples of every rung, so burn_in matters and
+    the weights cannot degenerate along the path.
+    Returns the dict of `parallel_tempering` with log_z, log_z0, log_z_se and se_rungs [R - 1] added (log_z is NaN when
+    the run was interrupted).
+    """
+    betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
+    if betas.size < 1 or betas[0] != 0.0:
+        raise ValueError("the ladder must start at beta_0 = 0, where log Z is known")
+    kw["all_rungs"] = True
+    res = parallel_tempering(hi, jij, q, n_ladders, betas, **kw)
+    h = np.asarray(hi, np.float32).astype(np.float64).reshape(-1, int(q))
+    m = h.max(axis=1)
+    res["log_z0"] = float(sum(m[i] + np.log(np.exp(h[i] - m[i]).sum()) for i in range(h.shape[0])))
+    if res["status"] == "converged":
+        res["log_z"], res["log_z_se"], res["se_rungs"] = tempered_log_z(res["e_j"], betas, res["log_z0"])
+    else:
+        res["log_z"], res["log_z_se"], res["se_rungs"] = float("nan"), float("nan"), np.full(betas.size - 1, np.nan)
+    return res
+
+
 def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, lr_decay_after=0, lambda_h=0.0,
            lambda_j=0.0, tol=0.0, seed=0, start=None, first_epoch=0, callback=None, device=0):
     """

@@ -3,12 +3,17 @@ Sample sequences from a fitted Potts model on the GPU:
 
     python -m evcouplings_amd.sample MODEL -n N -o OUT.a2m [--beta B] [--burn-in S] [--thin T] [--snapshots K]
                                      [--seed SEED] [--no-gaps] [--fix POS,POS,...] [--energies OUT.csv]
+                                     [--tempering R [--beta-max B]]
 
 MODEL is a plmc_v2 `.model` file (what `plmc -o` / `bin/plmc_hip -o` write).  N independent Gibbs chains run S burn-in
 sweeps; K snapshots of all chains, T sweeps apart, are written (N x K sequences).  The first record of OUT.a2m is the
 model's target sequence, named ID/start-end with the model's numbering, the samples follow.  --no-gaps never draws the
 first letter of the alphabet (the gap); --fix keeps the target's residue at the listed positions (the model's numbering).
 --energies writes one line per sample: id, H, H_J, H_h at beta = 1.
+--tempering R samples by parallel tempering instead: N independent ladders of R walkers at inverse temperatures on the
+couplings from 0 to B (--beta-max, default 1) that exchange after every sweep; S and T then count rounds, and the
+sequences written are those of the walker at B.  The acceptance rate of every pair of neighbouring temperatures goes to
+standard error.  It takes all letters at all positions: not with --no-gaps, --fix or --beta.
 """
 import argparse
 import sys
@@ -57,12 +62,29 @@ def main(argv=None):
     ap.add_argument("--fix", default="", help="comma-separated positions that keep the target's residue")
     ap.add_argument("--energies", default=None, help="CSV file for the energies of the samples")
     ap.add_argument("--id", default="SAMPLED", help="identifier of the first record")
+    ap.add_argument("--tempering", type=int, default=0, metavar="R",
+                    help="parallel tempering over R inverse temperatures on the couplings")
+    ap.add_argument("--beta-max", type=float, default=None, metavar="B", help="the top of the ladder (default 1)")
     a = ap.parse_args(argv)
+    if a.beta_max is not None and not a.tempering:
+        ap.error("--beta-max goes with --tempering")
+    if a.tempering and (a.tempering < 1 or a.no_gaps or a.fix.strip() or a.beta != 1.0):
+        ap.error("--tempering takes R >= 1 and goes without --no-gaps, --fix and --beta")
     model = model_from_file(a.model)
     fixed = [int(p) for p in a.fix.split(",") if p.strip()]
-    res = model_accel.sample_sequences(model, a.n, burn_in=a.burn_in, n_snapshots=a.snapshots, thin=a.thin, beta=a.beta,
-                                       seed=a.seed, fixed=fixed or None, exclude=model.alphabet[0] if a.no_gaps else "",
-                                       energies=a.energies is not None)
+    if a.tempering:
+        res = model_accel.sample_tempered(model, a.n, n_rungs=a.tempering,
+                                          beta_max=1.0 if a.beta_max is None else a.beta_max, burn_in=a.burn_in,
+                                          n_snapshots=a.snapshots, thin=a.thin, seed=a.seed,
+                                          energies=a.energies is not None, info=True)
+        sys.stderr.write("acceptance between neighbouring temperatures: %s\n"
+                         % " ".join("%.3f" % v for v in res[-1]["acceptance"]))
+        res = res[:-1] if a.energies is not None else res[0]
+    else:
+        res = model_accel.sample_sequences(model, a.n, burn_in=a.burn_in, n_snapshots=a.snapshots, thin=a.thin,
+                                           beta=a.beta, seed=a.seed, fixed=fixed or None,
+                                           exclude=model.alphabet[0] if a.no_gaps else "",
+                                           energies=a.energies is not None)
     samples, en = res if a.energies is not None else (res, None)
     write_a2m(a.o, model, samples, focus_id=a.id)
     if en is not None:

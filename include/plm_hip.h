@@ -419,6 +419,70 @@ typedef int (*plm_ais_cb)(int32_t steps_done, int32_t n_steps, void *user);
 int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_ais_opts *opts, int device,
             void *stream, plm_ais_cb cb, void *user, plm_ais_result *result);
 
+/* ---- parallel tempering: replica-exchange Gibbs sampling (DESIGN_NEXT_ROWS.md section 9.9) -------------------------
+ * Samples the family of plm_ais, p_beta(x) ~ exp(sum_i h_i(x_i) + beta sum_{i<j} J_ij(x_i, x_j)), at the R inverse
+ * temperatures of a ladder at once, and lets neighbouring temperatures exchange.  Ladder: R >= 1 float32 values
+ * 0 <= beta_0 <= ... <= beta_{R-1}, all finite; beta_0 need not be 0 and equal neighbours are allowed.
+ * Walkers: C independent ladders of R walkers.  Walker w = l R + s is slot s of ladder l, and chain w of the random
+ * numbers.  It carries its states, its tracked coupling energy E (float64) and its rung rho(w) in 0..R-1.  States never
+ * move between walkers: an exchange swaps rungs.  Per ladder the maps rung_of_slot and slot_of_rung are inverses.
+ * Start, start == NULL: rho(l R + s) = s; states from plm_sample's start rule at beta = 1 with all states allowed (sweep
+ * index 0xFFFFFFFF), E = 1/2 sum_i (double)U_i[x_i] from the measuring pass, all exactly as plm_ais.  start (C R x L
+ * states) given: rho from start_rungs (NULL: rho = s) and E from the measuring pass, or, with start_e, E as given: the
+ * bit-exact continuation of an earlier call from its walkers, rungs and walker_e with first_round moved on.
+ * Round: the global round number is g = first_round + the local number.
+ *   1. n = sweeps_per_round sweeps with the sweep indices g n .. g n + n - 1.  A site update of walker w is the one of
+ *      plm_ais at beta = beta_rho(w): U in float32 from 0 over j = 0 .. L-1, j != i; arg_a = fadd(h_i(a), fmul(beta, U_a));
+ *      the draw of plm_sample on arg with beta = 1; Philox counter (w, 0, sweep, site); E += (double)U[a_new] -
+ *      (double)U[a_old].
+ *   2. one exchange pass of parity p = g mod 2: for every ladder l and every r = p (mod 2) with r + 1 < R, a =
+ *      slot_of_rung[r], b = slot_of_rung[r + 1], Delta = ((double)beta_{r+1} - (double)beta_r) (E_a - E_b) (the two
+ *      differences, then one product, each rounded once), u = plm_sample's uniform of Philox word 0 at counter
+ *      (l, 1, g, r), same key, widened to double; accept iff Delta >= 0 or u < exp(Delta) in float64.  On acceptance the
+ *      two walkers swap rungs and accepts[r] goes up by one.  (The fields cancel in Delta: E holds the coupling part.)
+ * Schedule: burn_in rounds, then K = n_snapshots snapshots thin rounds apart: snapshot k is taken after burn_in + k thin
+ * rounds of the call (with burn_in = 0 snapshot 0 is the start); the call runs burn_in + (K - 1) thin rounds.  A snapshot
+ * holds, in rung order, the states and E of the walker at every rung: samples K x C x R x L, e_j K x C x R; with
+ * all_rungs == 0 rung R - 1 only: K x C x L and K x C.  attempts[r] = C x the rounds of the call whose parity is r mod 2.
+ * Ladder l depends on (seed, l, model, ladder, n, first_round and the start of that ladder) only: not on C, the launch
+ * plan or the run.  cb, if given, is called between rounds and cancels by returning non-zero: status
+ * PLM_STATUS_INTERRUPTED, rounds_done rounds ran, walkers, rungs, walker_e, accepts and attempts hold the state reached,
+ * snapshots not yet taken are zero.  Every output pointer may be NULL.
+ * PLM_EINVAL (before the device is looked at): NULL opts or result, sizes below 1, burn_in or first_round below 0, thin
+ * below 1; a ladder that is NULL, decreases, is negative or holds a non-finite value; (first_round + rounds + 1) n at or
+ * above 2^32 - 1; start_rungs without start, start_e without both; C R L at or above 2^31.  PLM_EUNSUPPORTED: q outside
+ * 2..32.  PLM_ENOMEM before any array is read; then PLM_EINVAL for start states outside 0..q-1 and for start_rungs that
+ * are not a permutation of 0..R-1 within each ladder. */
+typedef struct {
+    int32_t n_ladders;         /* C >= 1 independent ladders                                           */
+    int32_t n_rungs;           /* R >= 1 temperatures                                                  */
+    int32_t burn_in;           /* rounds before the first snapshot, >= 0                               */
+    int32_t n_snapshots;       /* K >= 1                                                               */
+    int32_t thin;              /* rounds between snapshots, >= 1                                       */
+    int32_t sweeps_per_round;  /* n >= 1                                                               */
+    int32_t first_round;       /* >= 0: global number of this call's first round (continuation)        */
+    int32_t all_rungs;         /* 0: snapshots hold rung R - 1 only; else every rung                   */
+    const float *betas;        /* R values as defined above                                            */
+    uint64_t seed;
+    const int8_t  *start;       /* NULL, or C R x L states of the walkers                              */
+    const int32_t *start_rungs; /* NULL, or C R rungs of the walkers                                   */
+    const double  *start_e;     /* NULL, or C R tracked energies of the walkers                        */
+} plm_pt_opts;
+typedef struct {
+    int8_t  *samples;          /* K x C x (R or 1) x L states in rung order, or NULL                   */
+    double  *e_j;              /* K x C x (R or 1) tracked coupling energies of those rows, or NULL    */
+    int64_t *accepts;          /* [R - 1] accepted exchanges between the rungs r and r + 1, or NULL    */
+    int64_t *attempts;         /* [R - 1] attempted ones, or NULL                                      */
+    int8_t  *walkers;          /* C R x L final states of the walkers, or NULL                         */
+    int32_t *rungs;            /* C R final rungs of the walkers, or NULL                              */
+    double  *walker_e;         /* C R final tracked energies of the walkers, or NULL                   */
+    int32_t rounds_done;
+    int32_t status;            /* PLM_STATUS_CONVERGED when all rounds ran, else PLM_STATUS_INTERRUPTED */
+} plm_pt_result;
+typedef int (*plm_pt_cb)(int32_t rounds_done, int32_t n_rounds, void *user);
+int plm_pt(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_pt_opts *opts, int device,
+           void *stream, plm_pt_cb cb, void *user, plm_pt_result *result);
+
 /* ---- mean-field direct coupling analysis ---------------------------
  * Replaces the arithmetic of evcouplings/couplings/mean_field.py:163-222 (MeanFieldDCA.fit: weights,
  * frequencies, pseudo-count regularisation :717-790, covariance matrix :897-940, J = -C^-1 :204-210 and
