@@ -4,12 +4,11 @@
 // Gibbs sweeps of plm_sample's contract with the temperature on the couplings only, and carries its coupling energy E
 // and its log weight in float64: log w += (beta_k - beta_{k-1}) E before the sweeps at beta_k.
 //
-//   k_ais          the tiled form: the pipeline of k_gibbs (plm_gibbs_device.h) with U starting at zero, the field added
-//                  after the loop, and E followed through U[a_new] - U[a_old], which the lane holds when it draws
+//   k_ais          the tiled form of the tempered sweep (plm_tempered_device.h) under the policy of this file
 //   k_ais_direct   the direct form: lanes = (chain, state), the two U by shuffles inside the group
 // A launch runs the steps [k0, k1) of the schedule; the first one draws the start states and measures E there.
 #include "plm_sample_internal.h"
-#include "plm_gibbs_device.h"
+#include "plm_tempered_device.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -18,223 +17,63 @@
 
 namespace {
 
-// The products and sums the contract states with one rounding each.  The _rn intrinsics of HIP are plain operators,
-// which the compiler fuses into one multiply-add with a single rounding; the pragma keeps the two roundings.
-__device__ __forceinline__ float field_plus_scaled(float h, float beta, float u) {
-#pragma clang fp contract(off)
-    const float p = beta * u;
-    return h + p;
-}
+// The product and the sum the contract states with one rounding each (see field_plus_scaled): the pragma keeps the
+// compiler from fusing them into one multiply-add.
 __device__ __forceinline__ double weight_step(double logw, double dbeta, double e) {
 #pragma clang fp contract(off)
     const double p = dbeta * e;
     return logw + p;
 }
 
-// U_a of a state known only at run time, as a chain of selects over the NV 4 registers (an indexed array would live in
-// scratch memory)
-template <int NV>
-__device__ __forceinline__ float pick_state(const float4 *U, int a) {
-    float r = 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-        r = a == 4 * v + 0 ? U[v].x : r;
-        r = a == 4 * v + 1 ? U[v].y : r;
-        r = a == 4 * v + 2 ? U[v].z : r;
-        r = a == 4 * v + 3 ? U[v].w : r;
+// The policy of the tempered body: the steps [k0, k1) of the schedule, n_per sweeps at betas[k + 1] after the weight
+// step of log w, one beta for the whole launch (a scalar register).  first != 0: the start rule, log w = 0 and E from
+// the measuring pass; otherwise states, E and log w are read, and all are written back.
+struct AisPolicy {
+    const float *betas;          // [K + 1]
+    int k0, k1, n_per, first;
+    double *e_io, *logw_io;      // [C]
+    double logw;
+    static constexpr bool three_start_modes = false;
+    __device__ __forceinline__ int start_mode() const { return first ? PT_START_RULE : PT_CONTINUE; }
+    __device__ __forceinline__ void begin(int, int) {}
+    __device__ __forceinline__ void read(int chain, double &E) {
+        E = e_io[chain];
+        logw = logw_io[chain];
     }
-    return r;
-}
-
-// U[a] = sum_{j != i} J_ij(a, x_j) of the lane's chain in float32, j = 0 .. L-1, from zero: the loop of k_gibbs
-#define AIS_SITE_U()                                                                    \
-    const float4 *Wi = W + (int64_t)i * L * row4;                                       \
-    float4 U[NV];                                                                       \
-    _Pragma("unroll") for (int v = 0; v < NV; v++) U[v] = make_float4(0.f, 0.f, 0.f, 0.f); \
-    PreSet pre0, pre1, pre2;                                                            \
-    GS_FETCH(0, pre0);                                                                  \
-    GS_FETCH(1, pre1);                                                                  \
-    GS_FETCH(2, pre2);                                                                  \
-    for (int base = 0; base < n_chunks; base += GS_DEPTH) {                             \
-        GS_STEP(base, pre0);                                                            \
-        GS_STEP(base + 1, pre1);                                                        \
-        GS_STEP(base + 2, pre2);                                                        \
+    __device__ __forceinline__ int first_step() const { return k0; }
+    __device__ __forceinline__ int end_step() const { return k1; }
+    __device__ __forceinline__ int n_sweeps() const { return n_per; }
+    __device__ __forceinline__ float beta(int k) const { return betas[k + 1]; }
+    __device__ __forceinline__ void before_sweeps(int k, float beta, double E) {
+        logw = weight_step(logw, (double)beta - (double)betas[k], E);
     }
+    __device__ __forceinline__ uint32_t sweep_index(int k, int s) const {
+        return (uint32_t)k * (uint32_t)n_per + (uint32_t)s;
+    }
+    __device__ __forceinline__ void write(int chain, double E) const {
+        e_io[chain] = E;
+        logw_io[chain] = logw;
+    }
+};
 
-// The LDS layout, the staging and the site order are those of k_gibbs.  states, E and logw are read (first == 0) and
-// written back; first != 0: the start rule at beta = 1, logw = 0 and E from a measuring pass over the sites.
 template <int NV, int TILE>
 __global__ __launch_bounds__(TILE) void k_ais(const float4 *__restrict__ W, int L, int q, int C, int JC,
                                               const float *__restrict__ betas /* [K + 1] */, int k0, int k1, int n_per,
                                               int first, uint32_t allowed, uint32_t seed_lo, uint32_t seed_hi,
                                               int8_t *__restrict__ states /* [C][L] */, double *__restrict__ e_io /* [C] */,
                                               double *__restrict__ logw_io /* [C] */) {
-    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;
-    extern __shared__ float4 lds4[];
-    const int tid = threadIdx.x;
-    const int L4 = (L + 3) >> 2;
-    const int c0 = blockIdx.x * TILE;
-    const int chain = c0 + tid;
-    const int n_here = min(TILE, C - c0);
-    const int buf_f4 = JC * q * NVP;
-    float4 *stage = lds4;
-    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);
-    uint32_t *xw = (uint32_t *)xs;
-    const float4 *H = W + (int64_t)L * L * q * NV;
-    const int n_chunks = (L + JC - 1) / JC;
-    const int row4 = q * NV;
-    uint32_t g = 0;
-
-    for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
-    __syncthreads();
-    double E = 0.0, logw = 0.0;
-    if (first) {
-        for (int i = 0; i < L; i++) {
-            float4 Hi[NV];
-#pragma unroll
-            for (int v = 0; v < NV; v++) Hi[v] = H[i * NV + v];
-            const int a = draw_state<NV>(Hi, q, allowed, 1.0f, philox_word0((uint32_t)chain, 0u, GS_START_SWEEP,
-                                                                            (uint32_t)i, seed_lo, seed_hi));
-            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;
-        }
-        __syncthreads();
-        for (int i = 0; i < L; i++) {                      // the measuring pass: no draws
-            AIS_SITE_U()
-            E += (double)pick_state<NV>(U, xs[((i >> 2) * TILE + tid) * 4 + (i & 3)]);
-        }
-        E *= 0.5;                                          // every pair was met from both of its sites
-    } else {
-        for (int k = tid; k < n_here * L; k += TILE) {
-            const int c = k / L, j = k - c * L;
-            xs[((j >> 2) * TILE + c) * 4 + (j & 3)] = (uint8_t)states[(int64_t)c0 * L + k];
-        }
-        if (chain < C) {
-            E = e_io[chain];
-            logw = logw_io[chain];
-        }
-        __syncthreads();
-    }
-
-    for (int k = k0; k < k1; k++) {
-        const float beta = betas[k + 1];
-        logw = weight_step(logw, (double)beta - (double)betas[k], E);
-        for (int s = 0; s < n_per; s++) {
-            const uint32_t sweep = (uint32_t)k * (uint32_t)n_per + (uint32_t)s;
-            for (int i = 0; i < L; i++) {
-                AIS_SITE_U()
-                float4 arg[NV];
-#pragma unroll
-                for (int v = 0; v < NV; v++) {
-                    const float4 hv = H[i * NV + v];
-                    arg[v].x = field_plus_scaled(hv.x, beta, U[v].x);
-                    arg[v].y = field_plus_scaled(hv.y, beta, U[v].y);
-                    arg[v].z = field_plus_scaled(hv.z, beta, U[v].z);
-                    arg[v].w = field_plus_scaled(hv.w, beta, U[v].w);
-                }
-                const int at = ((i >> 2) * TILE + tid) * 4 + (i & 3);
-                const int a_old = xs[at];
-                const int a = draw_state<NV>(arg, q, allowed, 1.0f,
-                                             philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
-                E += (double)pick_state<NV>(U, a) - (double)pick_state<NV>(U, a_old);
-                xs[at] = (uint8_t)a;                       // a lane reads only its own chain: no barrier
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < n_here * L; k += TILE) {
-        const int c = k / L, j = k - c * L;
-        states[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
-    }
-    if (chain < C) {
-        e_io[chain] = E;
-        logw_io[chain] = logw;
-    }
+    tempered_tile<NV, TILE>(W, L, q, C, JC, allowed, seed_lo, seed_hi, states,
+                            AisPolicy{betas, k0, k1, n_per, first, e_io, logw_io, 0.0});
 }
 
-// Lanes = (chain, state) as in k_gibbs_direct: lane a holds U_a, the two U of the energy step come from the lanes a_new
-// and a_old of the group.  Every lane of a group carries the same E and logw; lane 0 writes them.
 template <int QP>
 __global__ __launch_bounds__(256) void k_ais_direct(const float *__restrict__ Wf, int L, int q, int QS, int C,
                                                     const float *__restrict__ betas, int k0, int k1, int n_per, int first,
                                                     uint32_t allowed, uint32_t seed_lo, uint32_t seed_hi,
                                                     int8_t *__restrict__ states, double *__restrict__ e_io,
                                                     double *__restrict__ logw_io) {
-    constexpr int CPW = 256 / QP;
-    extern __shared__ float4 lds4[];
-    uint8_t *xs = (uint8_t *)lds4;
-    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;
-    const int lane0 = (tid & 63) & ~(QP - 1);              // the group's first lane within the wave
-    const int Lp = (L + 3) & ~3;
-    const int c0 = blockIdx.x * CPW;
-    const int chain = c0 + cl;
-    const int n_here = min(CPW, C - c0);
-    const float *Hf = Wf + (int64_t)L * L * q * QS;
-    uint8_t *xc = xs + cl * Lp;
-    for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
-    __syncthreads();
-    double E = 0.0, logw = 0.0;
-    if (first) {
-        for (int i = 0; i < L; i++) {
-            const float Hi = a < q ? Hf[i * QS + a] : 0.f;
-            const int x = draw_group<QP>(Hi, a, q, allowed, 1.0f,
-                                         philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i, seed_lo, seed_hi));
-            if (a == 0) xc[i] = (uint8_t)x;
-        }
-        __syncthreads();
-        for (int i = 0; i < L; i++) {
-            const float *Wi = Wf + (int64_t)i * L * q * QS;
-            float U = 0.f;
-            for (int j = 0; j < L; j++) {
-                if (j == i) continue;
-                const int x = xc[j];
-                if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-            }
-            E += (double)__shfl(U, lane0 + xc[i], 64);
-        }
-        E *= 0.5;
-    } else {
-        for (int k = tid; k < n_here * L; k += 256) {
-            const int c = k / L, j = k - c * L;
-            xs[c * Lp + j] = (uint8_t)states[(int64_t)c0 * L + k];
-        }
-        if (chain < C) {
-            E = e_io[chain];
-            logw = logw_io[chain];
-        }
-        __syncthreads();
-    }
-    for (int k = k0; k < k1; k++) {
-        const float beta = betas[k + 1];
-        logw = weight_step(logw, (double)beta - (double)betas[k], E);
-        for (int s = 0; s < n_per; s++) {
-            const uint32_t sweep = (uint32_t)k * (uint32_t)n_per + (uint32_t)s;
-            for (int i = 0; i < L; i++) {
-                const float *Wi = Wf + (int64_t)i * L * q * QS;
-                float U = 0.f;
-                for (int j = 0; j < L; j++) {
-                    if (j == i) continue;
-                    const int x = xc[j];
-                    if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-                }
-                const float arg = a < q ? field_plus_scaled(Hf[i * QS + a], beta, U) : 0.f;
-                const int x_old = xc[i];
-                const int x = draw_group<QP>(arg, a, q, allowed, 1.0f,
-                                             philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
-                E += (double)__shfl(U, lane0 + x, 64) - (double)__shfl(U, lane0 + x_old, 64);
-                if (a == 0) xc[i] = (uint8_t)x;            // the group is inside one wave: its lanes have read x_old
-                __syncthreads();
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < n_here * L; k += 256) {
-        const int c = k / L, j = k - c * L;
-        states[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
-    }
-    if (a == 0 && chain < C) {
-        e_io[chain] = E;
-        logw_io[chain] = logw;
-    }
+    tempered_direct<QP>(Wf, L, q, QS, C, allowed, seed_lo, seed_hi, states,
+                        AisPolicy{betas, k0, k1, n_per, first, e_io, logw_io, 0.0});
 }
 
 struct AisArgs {

@@ -1,6 +1,7 @@
-// plm_gibbs_device.h -- the device code the sweep kernels of plm_sample.hip and plm_ais.hip share: the Philox block,
-// the uniform, the draw of the contract in its two forms, and the staging pipeline of the tiled form (DESIGN_NEXT_ROWS.md
-// section 9.6).  Included by those two files only; everything here has internal linkage.
+// plm_gibbs_device.h -- the device code every sweep kernel shares: the Philox block, the uniform, the draw of the
+// contract in its two forms, and the staging pipeline of the tiled form (DESIGN_NEXT_ROWS.md section 9.6).  Included by
+// plm_sample.hip (k_gibbs*) and, through plm_tempered_device.h, by plm_ais.hip and plm_pt.hip; everything here has
+// internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -133,6 +134,24 @@ _Pragma("unroll") \
                         } \
                     } \
     } while (0)
+
+// The pipeline of site i: U[a] = init + sum_{j != i} J_ij(a, x_j) of the lane's chain in float32, j = 0 .. L-1, with
+// init a float4 expression in v (the fields for k_gibbs, zero for the tempered sweeps).  GS_DEPTH chunks are in flight
+// in registers (one LDS round trip per chunk would leave the sweep bound by the latency of the loads: measured,
+// section 9.6).  Declares Wi and U; the rest are the locals of the tiled kernels by name.
+#define GS_SITE_U(init)                                                                 \
+    const float4 *Wi = W + (int64_t)i * L * row4;                                       \
+    float4 U[NV];                                                                       \
+    _Pragma("unroll") for (int v = 0; v < NV; v++) U[v] = (init);                       \
+    PreSet pre0, pre1, pre2;                                                            \
+    GS_FETCH(0, pre0);                                                                  \
+    GS_FETCH(1, pre1);                                                                  \
+    GS_FETCH(2, pre2);                                                                  \
+    for (int base = 0; base < n_chunks; base += GS_DEPTH) {                             \
+        GS_STEP(base, pre0);                                                            \
+        GS_STEP(base + 1, pre1);                                                        \
+        GS_STEP(base + 2, pre2);                                                        \
+    }
 
 // The same draw with one lane per state (groups of QP lanes, QP a power of two >= q): the maximum by a butterfly, the
 // running sum by every lane of the group in state order -- the same additions in the same order as draw_state, so the

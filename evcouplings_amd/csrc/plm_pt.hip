@@ -5,13 +5,14 @@
 // every walker at the beta of its rung, then one exchange pass between neighbouring rungs of the round's parity; an
 // exchange swaps rungs, never states.
 //
-//   k_pt           the tiled form: k_ais with the lane's own beta, read through the walker's rung, and no log weight
+//   k_pt           the tiled form of the tempered sweep (plm_tempered_device.h), the body of k_ais, under the policy of
+//                  this file: the lane's own beta, read through the walker's rung, and no log weight
 //   k_pt_direct    the direct form: lanes = (walker, state), the same additions in the same order
 //   k_pt_swap      one thread per (ladder, pair) of the round's parity; the pairs of one pass are disjoint
 //   k_pt_snapshot  states and E in rung order into the output of one snapshot
 // The loop over the rounds is enqueued without a host wait unless there is a callback, and allocates nothing.
 #include "plm_sample_internal.h"
-#include "plm_gibbs_device.h"
+#include "plm_tempered_device.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -20,18 +21,8 @@
 
 namespace {
 
-// how a launch of the sweep kernels comes by its states and E
-enum { PT_CONTINUE = 0,      // states and E from global memory
-       PT_START_RULE = 1,    // the sampler's start rule at beta = 1, E from a measuring pass
-       PT_MEASURE = 2 };     // states from global memory, E from a measuring pass
-
-// The products and sums the contract states with one rounding each (see plm_ais.hip): the pragma keeps the compiler
-// from fusing them into one multiply-add.
-__device__ __forceinline__ float field_plus_scaled(float h, float beta, float u) {
-#pragma clang fp contract(off)
-    const float p = beta * u;
-    return h + p;
-}
+// The differences and the product the contract states with one rounding each: the pragma keeps the compiler from
+// fusing them (see field_plus_scaled).
 __device__ __forceinline__ double exchange_delta(double beta_hi, double beta_lo, double e_a, double e_b) {
 #pragma clang fp contract(off)
     const double db = beta_hi - beta_lo;
@@ -39,197 +30,48 @@ __device__ __forceinline__ double exchange_delta(double beta_hi, double beta_lo,
     return db * de;
 }
 
-// U_a of a state known only at run time, as a chain of selects over the NV 4 registers (an indexed array would live in
-// scratch memory)
-template <int NV>
-__device__ __forceinline__ float pick_state(const float4 *U, int a) {
-    float r = 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-        r = a == 4 * v + 0 ? U[v].x : r;
-        r = a == 4 * v + 1 ? U[v].y : r;
-        r = a == 4 * v + 2 ? U[v].z : r;
-        r = a == 4 * v + 3 ? U[v].w : r;
-    }
-    return r;
-}
+// The policy of the tempered body: one step of n_sweeps sweeps with the indices sweep0 .. (none: a launch that only
+// starts the walkers), every lane at the beta of its own walker's rung (a vector register), E the only scalar of a
+// walker.  A lane beyond C in the last tile reads no rung.
+struct PtPolicy {
+    const float *ladder;         // [R]
+    const int *rung_of_slot;     // [C]
+    uint32_t sweep0;
+    int n, mode;
+    double *e_io;                // [C]
+    float lane_beta;
+    static constexpr bool three_start_modes = true;
+    __device__ __forceinline__ int start_mode() const { return mode; }
+    __device__ __forceinline__ void begin(int chain, int C) { lane_beta = chain < C ? ladder[rung_of_slot[chain]] : 0.f; }
+    __device__ __forceinline__ void read(int chain, double &E) const { E = e_io[chain]; }
+    __device__ __forceinline__ int first_step() const { return 0; }
+    __device__ __forceinline__ int end_step() const { return 1; }
+    __device__ __forceinline__ int n_sweeps() const { return n; }
+    __device__ __forceinline__ float beta(int) const { return lane_beta; }
+    __device__ __forceinline__ void before_sweeps(int, float, double) const {}
+    __device__ __forceinline__ uint32_t sweep_index(int, int s) const { return sweep0 + (uint32_t)s; }
+    __device__ __forceinline__ void write(int chain, double E) const { e_io[chain] = E; }
+};
 
-// U[a] = sum_{j != i} J_ij(a, x_j) of the lane's walker in float32, j = 0 .. L-1, from zero: the loop of k_gibbs
-#define PT_SITE_U()                                                                     \
-    const float4 *Wi = W + (int64_t)i * L * row4;                                       \
-    float4 U[NV];                                                                       \
-    _Pragma("unroll") for (int v = 0; v < NV; v++) U[v] = make_float4(0.f, 0.f, 0.f, 0.f); \
-    PreSet pre0, pre1, pre2;                                                            \
-    GS_FETCH(0, pre0);                                                                  \
-    GS_FETCH(1, pre1);                                                                  \
-    GS_FETCH(2, pre2);                                                                  \
-    for (int base = 0; base < n_chunks; base += GS_DEPTH) {                             \
-        GS_STEP(base, pre0);                                                            \
-        GS_STEP(base + 1, pre1);                                                        \
-        GS_STEP(base + 2, pre2);                                                        \
-    }
-
-// The LDS layout, the staging and the site order are those of k_gibbs and k_ais.  C counts walkers (ladders x rungs).
-// n_sweeps sweeps with the indices sweep0 .. (none: a launch that only starts the walkers).  A lane beyond C in the last
-// tile reads no rung and writes nothing.
+// C counts walkers (ladders x rungs)
 template <int NV, int TILE>
 __global__ __launch_bounds__(TILE) void k_pt(const float4 *__restrict__ W, int L, int q, int C, int JC,
                                              const float *__restrict__ ladder /* [R] */,
                                              const int *__restrict__ rung_of_slot /* [C] */, uint32_t sweep0, int n_sweeps,
                                              int mode, uint32_t allowed, uint32_t seed_lo, uint32_t seed_hi,
                                              int8_t *__restrict__ states /* [C][L] */, double *__restrict__ e_io /* [C] */) {
-    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;
-    extern __shared__ float4 lds4[];
-    const int tid = threadIdx.x;
-    const int L4 = (L + 3) >> 2;
-    const int c0 = blockIdx.x * TILE;
-    const int chain = c0 + tid;
-    const int n_here = min(TILE, C - c0);
-    const int buf_f4 = JC * q * NVP;
-    float4 *stage = lds4;
-    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);
-    uint32_t *xw = (uint32_t *)xs;
-    const float4 *H = W + (int64_t)L * L * q * NV;
-    const int n_chunks = (L + JC - 1) / JC;
-    const int row4 = q * NV;
-    uint32_t g = 0;
-    const float beta = chain < C ? ladder[rung_of_slot[chain]] : 0.f;
-
-    for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
-    __syncthreads();
-    if (mode == PT_START_RULE) {
-        for (int i = 0; i < L; i++) {
-            float4 Hi[NV];
-#pragma unroll
-            for (int v = 0; v < NV; v++) Hi[v] = H[i * NV + v];
-            const int a = draw_state<NV>(Hi, q, allowed, 1.0f, philox_word0((uint32_t)chain, 0u, GS_START_SWEEP,
-                                                                            (uint32_t)i, seed_lo, seed_hi));
-            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;
-        }
-    } else {
-        for (int k = tid; k < n_here * L; k += TILE) {
-            const int c = k / L, j = k - c * L;
-            xs[((j >> 2) * TILE + c) * 4 + (j & 3)] = (uint8_t)states[(int64_t)c0 * L + k];
-        }
-    }
-    __syncthreads();
-    double E = 0.0;
-    if (mode == PT_CONTINUE) {
-        if (chain < C) E = e_io[chain];
-    } else {
-        for (int i = 0; i < L; i++) {                      // the measuring pass: no draws
-            PT_SITE_U()
-            E += (double)pick_state<NV>(U, xs[((i >> 2) * TILE + tid) * 4 + (i & 3)]);
-        }
-        E *= 0.5;                                          // every pair was met from both of its sites
-    }
-
-    for (int s = 0; s < n_sweeps; s++) {
-        const uint32_t sweep = sweep0 + (uint32_t)s;
-        for (int i = 0; i < L; i++) {
-            PT_SITE_U()
-            float4 arg[NV];
-#pragma unroll
-            for (int v = 0; v < NV; v++) {
-                const float4 hv = H[i * NV + v];
-                arg[v].x = field_plus_scaled(hv.x, beta, U[v].x);
-                arg[v].y = field_plus_scaled(hv.y, beta, U[v].y);
-                arg[v].z = field_plus_scaled(hv.z, beta, U[v].z);
-                arg[v].w = field_plus_scaled(hv.w, beta, U[v].w);
-            }
-            const int at = ((i >> 2) * TILE + tid) * 4 + (i & 3);
-            const int a_old = xs[at];
-            const int a = draw_state<NV>(arg, q, allowed, 1.0f,
-                                         philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
-            E += (double)pick_state<NV>(U, a) - (double)pick_state<NV>(U, a_old);
-            xs[at] = (uint8_t)a;                           // a lane reads only its own walker: no barrier
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < n_here * L; k += TILE) {
-        const int c = k / L, j = k - c * L;
-        states[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
-    }
-    if (chain < C) e_io[chain] = E;
+    tempered_tile<NV, TILE>(W, L, q, C, JC, allowed, seed_lo, seed_hi, states,
+                            PtPolicy{ladder, rung_of_slot, sweep0, n_sweeps, mode, e_io, 0.f});
 }
 
-// Lanes = (walker, state) as in k_ais_direct: lane a holds U_a, the two U of the energy step come from the lanes a_new
-// and a_old of the group.  Every lane of a group carries the same beta and E; lane 0 writes E.
 template <int QP>
 __global__ __launch_bounds__(256) void k_pt_direct(const float *__restrict__ Wf, int L, int q, int QS, int C,
                                                    const float *__restrict__ ladder, const int *__restrict__ rung_of_slot,
                                                    uint32_t sweep0, int n_sweeps, int mode, uint32_t allowed,
                                                    uint32_t seed_lo, uint32_t seed_hi, int8_t *__restrict__ states,
                                                    double *__restrict__ e_io) {
-    constexpr int CPW = 256 / QP;
-    extern __shared__ float4 lds4[];
-    uint8_t *xs = (uint8_t *)lds4;
-    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;
-    const int lane0 = (tid & 63) & ~(QP - 1);              // the group's first lane within the wave
-    const int Lp = (L + 3) & ~3;
-    const int c0 = blockIdx.x * CPW;
-    const int chain = c0 + cl;
-    const int n_here = min(CPW, C - c0);
-    const float *Hf = Wf + (int64_t)L * L * q * QS;
-    uint8_t *xc = xs + cl * Lp;
-    const float beta = chain < C ? ladder[rung_of_slot[chain]] : 0.f;
-    for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
-    __syncthreads();
-    if (mode == PT_START_RULE) {
-        for (int i = 0; i < L; i++) {
-            const float Hi = a < q ? Hf[i * QS + a] : 0.f;
-            const int x = draw_group<QP>(Hi, a, q, allowed, 1.0f,
-                                         philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i, seed_lo, seed_hi));
-            if (a == 0) xc[i] = (uint8_t)x;
-        }
-    } else {
-        for (int k = tid; k < n_here * L; k += 256) {
-            const int c = k / L, j = k - c * L;
-            xs[c * Lp + j] = (uint8_t)states[(int64_t)c0 * L + k];
-        }
-    }
-    __syncthreads();
-    double E = 0.0;
-    if (mode == PT_CONTINUE) {
-        if (chain < C) E = e_io[chain];
-    } else {
-        for (int i = 0; i < L; i++) {
-            const float *Wi = Wf + (int64_t)i * L * q * QS;
-            float U = 0.f;
-            for (int j = 0; j < L; j++) {
-                if (j == i) continue;
-                const int x = xc[j];
-                if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-            }
-            E += (double)__shfl(U, lane0 + xc[i], 64);
-        }
-        E *= 0.5;
-    }
-    for (int s = 0; s < n_sweeps; s++) {
-        const uint32_t sweep = sweep0 + (uint32_t)s;
-        for (int i = 0; i < L; i++) {
-            const float *Wi = Wf + (int64_t)i * L * q * QS;
-            float U = 0.f;
-            for (int j = 0; j < L; j++) {
-                if (j == i) continue;
-                const int x = xc[j];
-                if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-            }
-            const float arg = a < q ? field_plus_scaled(Hf[i * QS + a], beta, U) : 0.f;
-            const int x_old = xc[i];
-            const int x = draw_group<QP>(arg, a, q, allowed, 1.0f,
-                                         philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
-            E += (double)__shfl(U, lane0 + x, 64) - (double)__shfl(U, lane0 + x_old, 64);
-            if (a == 0) xc[i] = (uint8_t)x;                // the group is inside one wave: its lanes have read x_old
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < n_here * L; k += 256) {
-        const int c = k / L, j = k - c * L;
-        states[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
-    }
-    if (a == 0 && chain < C) e_io[chain] = E;
+    tempered_direct<QP>(Wf, L, q, QS, C, allowed, seed_lo, seed_hi, states,
+                        PtPolicy{ladder, rung_of_slot, sweep0, n_sweeps, mode, e_io, 0.f});
 }
 
 // The exchange pass of global round g: blockIdx.y (and its stride) counts the pairs of the round's parity, between the

@@ -107,21 +107,7 @@ __global__ __launch_bounds__(TILE) void k_gibbs(const float4 *__restrict__ W, in
         const uint32_t sweep = sweep0 + (uint32_t)s;
         for (int i = 0; i < L; i++) {
             if (fixed && fixed[i]) continue;                  // uniform over the workgroup
-            const float4 *Wi = W + (int64_t)i * L * row4;
-            float4 U[NV];
-#pragma unroll
-            for (int v = 0; v < NV; v++) U[v] = H[i * NV + v];
-            // GS_DEPTH chunks are in flight in registers (one LDS round trip per chunk would leave the sweep bound by
-            // the latency of the loads: measured, section 9.6)
-            PreSet pre0, pre1, pre2;
-            GS_FETCH(0, pre0);
-            GS_FETCH(1, pre1);
-            GS_FETCH(2, pre2);
-            for (int base = 0; base < n_chunks; base += GS_DEPTH) {
-                GS_STEP(base, pre0);
-                GS_STEP(base + 1, pre1);
-                GS_STEP(base + 2, pre2);
-            }
+            GS_SITE_U(H[i * NV + v])
             const int a = draw_state<NV>(U, q, allowed, beta,
                                          philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
             xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;   // a lane reads only its own chain: no barrier

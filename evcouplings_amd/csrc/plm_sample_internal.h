@@ -1,6 +1,6 @@
-// plm_sample_internal.h -- what plm_sample.hip shares with plm_ais.hip and plm_bm.hip: the checks the three entry points
-// open with, the plan, the expansion of the couplings, the sweep launchers, and the step from a plan to the template
-// arguments of a sweep kernel.
+// plm_sample_internal.h -- what plm_sample.hip shares with plm_ais.hip, plm_pt.hip and plm_bm.hip: the checks the four
+// entry points (plm_sample, plm_ais, plm_pt, plm_bm_fit) open with, the plan, the expansion of the couplings, the sweep
+// launchers, and the step from a plan to the template arguments of a sweep kernel.
 #pragma once
 #include "plm_host_util.h"
 #include <type_traits>
@@ -13,7 +13,7 @@ struct SweepPlan {
     bool direct;                // the direct form instead (tile = chains per workgroup = 256 / lanes per chain)
 };
 
-// ---- the front matter of plm_sample, plm_ais and plm_bm_fit ----
+// ---- the front matter of plm_sample, plm_ais, plm_pt and plm_bm_fit ----
 int check_states(int q, const char *who);             // 2..32 states, or PLM_EUNSUPPORTED
 int check_chain_sites(int C, int L);                  // n_chains x n_sites < 2^31, or PLM_EINVAL
 double table_bytes(int L, int q);                     // the expanded table
