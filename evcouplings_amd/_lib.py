@@ -128,6 +128,14 @@ class PlmPtResult(C.Structure):
 
 PT_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
 
+IDENT_DENOM = {"columns": 0, "both": 1, "shorter": 2}
+
+
+class PlmIdentOpts(C.Structure):
+    _fields_ = [("gap_state", C.c_int32), ("denominator", C.c_int32), ("exclude_self", C.c_int32),
+                ("threshold", C.c_double)]
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -169,6 +177,9 @@ SYMBOLS = [
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),
     ("plm_alignment_stats", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int, _P]),
+    ("plm_cross_identities", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(PlmIdentOpts), _P, _P, _P, _P,
+                                       C.c_int, _P]),
+    ("plm_redundancy_filter", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(PlmIdentOpts), _P, _P, C.c_int, _P]),
     ("plm_fasta_split", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P, _P]),
     ("plm_encode_columns", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("plm_write_raw_ec_file", C.c_int, [C.c_char_p, C.c_int32, _P, C.c_char_p, _P]),

@@ -166,14 +166,59 @@ def alignment_filters(matrix_mapped, gap_state=0, minimum_sequence_coverage=None
     return keep, lc_cols
 
 
+def _mapped_with_gap(alignment):
+    """Alignment.matrix_mapped (made with map_matrix where the object has not mapped itself yet) and the state its
+    alphabet gives the match gap."""
+    mapped = alignment.matrix_mapped
+    if mapped is None:
+        mapped = map_matrix(alignment.matrix, alignment.alphabet_map)
+    return _int8_states(mapped, "matrix_mapped"), int(alignment.alphabet_map[alignment._match_gap])
+
+
+def nearest_identities(alignment_a, alignment_b, threshold=0.8, denominator="columns", device=0):
+    """For every sequence of alignment_a the nearest sequence of alignment_b (two reference `Alignment` objects over
+    the same columns): the dict of plm.cross_identities -- best_index, best_match, best_denom, n_within, identity --
+    computed on the mapped matrices with the alignment's own gap as the gap state."""
+    from evcouplings_amd import plm
+    a, gap = _mapped_with_gap(alignment_a)
+    b, gap_b = _mapped_with_gap(alignment_b)
+    if gap != gap_b:
+        raise ValueError("the two alignments map the gap to different states (%d, %d)" % (gap, gap_b))
+    return plm.cross_identities(a, b, threshold=threshold, gap_state=gap, denominator=denominator, device=device)
+
+
+def filter_redundant(alignment, threshold, denominator="columns", device=0):
+    """alignment.select(sequences=mask) with the mask of plm.redundancy_filter: in input order, a sequence goes when a
+    kept earlier one is within `threshold` (a fraction) of it; the first sequence always stays."""
+    from evcouplings_amd import plm
+    m, gap = _mapped_with_gap(alignment)
+    mask = plm.redundancy_filter(m, threshold, gap_state=gap, denominator=denominator, device=device)
+    return alignment.select(sequences=mask)
+
+
+# Drop-in for evcouplings.align.tools.run_hhfilter without HHsuite.  NOT VERIFIED AGAINST HHSUITE (no hhfilter binary
+# exists where this project is built): the denominator of the identity ("shorter" by recollection only, hence the
+# switch), the pair exactly at the threshold and the visiting order are assumptions, stated in its docstring.
+from evcouplings_amd.seqfilter import run_hhfilter  # noqa: E402,F401
+
+_ORIGINAL_HHFILTER = {}
+
 _NAMES = ("num_cluster_members", "frequencies", "pair_frequencies", "identities_to_seq", "map_matrix")
 
 
-def install(alignment_module=None):
+def install(alignment_module=None, redundancy_filter=False, tools_module=None):
     """Rebind the five functions in evcouplings.align.alignment (or the module given).  With them the arithmetic of
     the align stage's modify_alignment / describe_frequencies / describe_seq_identities / describe_coverage
     (align/protocol.py:463-640, 806-1016) -- weights, frequencies, identities to the query, the encoding of the
-    character matrix -- runs through this package; the reference code around it is unchanged."""
+    character matrix -- runs through this package; the reference code around it is unchanged.  redundancy_filter=True
+    also rebinds run_hhfilter in evcouplings.align.tools (or tools_module), which modify_alignment calls when
+    `seqid_filter` is set (align/protocol.py:884-900), to the drop-in above; the default leaves it alone."""
+    if redundancy_filter:
+        if tools_module is None:
+            import evcouplings.align.tools as tools_module
+        if tools_module not in _ORIGINAL_HHFILTER:
+            _ORIGINAL_HHFILTER[tools_module] = tools_module.run_hhfilter
+        tools_module.run_hhfilter = run_hhfilter
     if alignment_module is None:
         import evcouplings.align.alignment as alignment_module
     if alignment_module not in _ORIGINAL:
@@ -192,6 +237,8 @@ def install(alignment_module=None):
 
 
 def uninstall(alignment_module=None):
+    for tools_module in list(_ORIGINAL_HHFILTER):
+        tools_module.run_hhfilter = _ORIGINAL_HHFILTER.pop(tools_module)
     if alignment_module is None:
         import evcouplings.align.alignment as alignment_module
     if alignment_module in _ORIGINAL:

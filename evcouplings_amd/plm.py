@@ -133,6 +133,55 @@ def alignment_stats(msa, gap_state=0, query=None, device=0):
     return seq_gaps, col_gaps, ident
 
 
+def _ident_opts(threshold, gap_state, denominator, exclude_self):
+    if denominator not in _lib.IDENT_DENOM:
+        raise ValueError("denominator must be one of %s (got %r)" % (sorted(_lib.IDENT_DENOM), denominator))
+    return _lib.PlmIdentOpts(-1 if gap_state is None else int(gap_state), _lib.IDENT_DENOM[denominator],
+                             1 if exclude_self else 0, float(threshold))
+
+
+def cross_identities(a, b=None, threshold=0.8, gap_state=None, denominator="columns", exclude_self=None, device=0):
+    """
+    For every row of `a` (n_a x L integer states 0..126) the nearest row of `b` and the number of rows of `b` within
+    `threshold`; b=None compares `a` with itself, each row's own index left out (exclude_self defaults to that).
+    m = matching columns (with `gap_state`, a column where either row has the gap is no match), d = the denominator:
+    "columns" L, "both" the columns where neither row has the gap, "shorter" min(residues of the two rows); the last
+    two need a gap state.  Similar: "columns" m >= ceil(threshold L - 1e-9) (the rule of `reweight`), otherwise d > 0
+    and m >= ceil(threshold d - 1e-9).  Nearest: largest m / d compared exactly, ties to the smallest index.
+    Returns a dict of int32 arrays best_index (-1 where no partner is left), best_match, best_denom, n_within, and
+    identity = best_match / max(best_denom, 1) as float64.
+    """
+    lib = _lib.load()
+    a = _msa(a)
+    if exclude_self is None:
+        exclude_self = b is None
+    b = a if b is None else _msa(b)
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("a has %d columns, b has %d" % (a.shape[1], b.shape[1]))
+    opts = _ident_opts(threshold, gap_state, denominator, exclude_self)
+    out = {k: np.zeros(a.shape[0], np.int32) for k in ("best_index", "best_match", "best_denom", "n_within")}
+    check(lib.plm_cross_identities(_ptr(a), a.shape[0], _ptr(b), b.shape[0], a.shape[1], C.byref(opts),
+                                   _ptr(out["best_index"]), _ptr(out["best_match"]), _ptr(out["best_denom"]),
+                                   _ptr(out["n_within"]), int(device), None))
+    out["identity"] = out["best_match"] / np.maximum(out["best_denom"], 1).astype(np.float64)
+    return out
+
+
+def redundancy_filter(msa, threshold, gap_state=None, denominator="columns", device=0):
+    """
+    Greedy redundancy filter in input order: row 0 is kept, row s is kept iff no kept earlier row is similar to it
+    (similarity as in `cross_identities`).  Returns the boolean mask of kept rows; exactly the sequential definition.
+    """
+    lib = _lib.load()
+    msa = _msa(msa)
+    opts = _ident_opts(threshold, gap_state, denominator, False)
+    keep = np.zeros(msa.shape[0], np.uint8)
+    n_kept = C.c_int32(0)
+    check(lib.plm_redundancy_filter(_ptr(msa), msa.shape[0], msa.shape[1], C.byref(opts), _ptr(keep), C.byref(n_kept),
+                                    int(device), None))
+    return keep.astype(bool)
+
+
 def hamiltonians(seqs, q, hi, jij, device=0):
     """
     Statistical energies of sequences under a model: n x 3 float64 (H, H_J, H_h) with

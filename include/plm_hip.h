@@ -518,6 +518,40 @@ int plm_direct_information(const double *jij_full, const double *fi, int32_t n_s
 int plm_alignment_stats(const int8_t *msa, int32_t n_seqs, int32_t n_sites, int32_t gap_state, const int8_t *query,
                         int32_t *seq_gaps, int32_t *col_gaps, int32_t *ident, int device, void *stream);
 
+/* ---- pairwise identities between two sets of sequences, and the greedy redundancy filter built on them -------------
+ * For rows s of a and t of b over the n_sites columns (states 0..126, row-major):
+ *   m(s,t) = #{columns where both rows hold the same state}; with a gap state, a column where either row has the gap
+ *            is no match (gap_state = -1: gaps are ordinary states)
+ *   d(s,t) = PLM_IDENT_DENOM_COLUMNS: n_sites;  _BOTH: #{columns where neither row has the gap};
+ *            _SHORTER: min(residues of s, residues of t)            (_BOTH and _SHORTER need a gap state)
+ *   similar: _COLUMNS: m >= ceil(threshold * n_sites - 1e-9), the threshold of plm_reweight (a == b, no gap state:
+ *            n_within equals its counts); _BOTH / _SHORTER: d > 0 and m >= ceil(threshold * d - 1e-9)
+ *   nearest: the pair with the largest m / d, compared exactly (m1 d2 against m2 d1 in 64 bits; d = 0 is identity 0),
+ *            ties to the smallest t.
+ * plm_cross_identities: best_index / best_match / best_denom [n_a] describe the nearest row of b (index -1, 0, 0 when
+ * exclude_self leaves no partner), n_within [n_a] counts the similar rows; exclude_self (a and b hold the same rows)
+ * skips t == s in both.  Any output may be NULL.  The result does not depend on how the rows of b are split over
+ * workgroups; PLM_IDENT_TPER (rows of b per workgroup, an integer >= 1; measurements and tests) forces the split.
+ * plm_redundancy_filter: keep_out[0] = 1, keep_out[s] = 1 iff no kept t < s is similar to s (exclude_self is ignored),
+ * exactly the sequential definition; n_kept may be NULL.  Device memory is O(n_seqs n_sites), no pair matrix.
+ * PLM_EINVAL (before the device is looked at): NULL inputs or opts, an empty set or one of more than 2^30 rows, states
+ * outside 0..126, gap_state outside -1..126, an unknown denominator or one that needs a gap state without one, a
+ * threshold that is not finite, a PLM_IDENT_TPER that is no positive integer.  PLM_ENOMEM before any allocation.     */
+#define PLM_IDENT_DENOM_COLUMNS 0
+#define PLM_IDENT_DENOM_BOTH 1
+#define PLM_IDENT_DENOM_SHORTER 2
+typedef struct {
+    int32_t gap_state;      /* -1: none */
+    int32_t denominator;    /* PLM_IDENT_DENOM_* */
+    int32_t exclude_self;   /* cross call with a == b */
+    double threshold;
+} plm_ident_opts;
+int plm_cross_identities(const int8_t *a, int32_t n_a, const int8_t *b, int32_t n_b, int32_t n_sites,
+                         const plm_ident_opts *opts, int32_t *best_index, int32_t *best_match, int32_t *best_denom,
+                         int32_t *n_within, int device, void *stream);
+int plm_redundancy_filter(const int8_t *msa, int32_t n_seqs, int32_t n_sites, const plm_ident_opts *opts,
+                          uint8_t *keep_out, int32_t *n_kept, int device, void *stream);
+
 /* ---- alignment input (host code, no device): what plmc does when it reads the file run_plmc names (tools.py:202-262
  * passes only the path).  evcouplings_amd/alignment_io.py states the rules and keeps a pure-Python twin (fallback and
  * test oracle); these two single passes replace its per-line loop and fancy indexing (0.23 -> 0.03 s at the headline).
