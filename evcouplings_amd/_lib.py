@@ -136,6 +136,13 @@ class PlmIdentOpts(C.Structure):
                 ("threshold", C.c_double)]
 
 
+TRIPLET_COUNTS, TRIPLET_FREQ, TRIPLET_CONNECTED = 1, 2, 4
+
+
+class PlmTripletOpts(C.Structure):
+    _fields_ = [("skip_state", C.c_int32), ("want", C.c_int32)]
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -180,6 +187,10 @@ SYMBOLS = [
     ("plm_cross_identities", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(PlmIdentOpts), _P, _P, _P, _P,
                                        C.c_int, _P]),
     ("plm_redundancy_filter", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(PlmIdentOpts), _P, _P, C.c_int, _P]),
+    ("plm_triplet_stats", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(PlmTripletOpts), _P,
+                                    _P, _P, C.POINTER(C.c_uint64), C.c_int, _P]),
+    ("plm_triplet_scan", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(PlmTripletOpts), _P,
+                                   _P, _P, C.POINTER(C.c_uint64), C.c_int, _P]),
     ("plm_fasta_split", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P, _P]),
     ("plm_encode_columns", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("plm_write_raw_ec_file", C.c_int, [C.c_char_p, C.c_int32, _P, C.c_char_p, _P]),

@@ -182,6 +182,74 @@ def redundancy_filter(msa, threshold, gap_state=None, denominator="columns", dev
     return keep.astype(bool)
 
 
+def triplet_index(sites_or_L):
+    """The (T, 3) int32 table of every i < j < k among the given sites (an ascending sequence, or L for range(L)),
+    lexicographic: the order of `triplet_scan`'s outputs.  Pure numpy."""
+    sites = np.arange(int(sites_or_L)) if np.ndim(sites_or_L) == 0 else np.asarray(sites_or_L)
+    n = len(sites)
+    i, j = np.triu_indices(n, 1)                     # the pairs in row-major order; pair (i, j) has n - 1 - j values of k
+    cnt = n - 1 - j
+    ii, jj = np.repeat(i, cnt), np.repeat(j, cnt)
+    kk = np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt) + jj + 1
+    return np.stack([sites[ii], sites[jj], sites[kk]], axis=1).astype(np.int32).reshape(-1, 3)
+
+
+def _triplet_args(msa, weights, skip_state, want):
+    msa = _msa(msa)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+    if w is not None and w.shape != (msa.shape[0],):
+        raise ValueError("weights must hold one value per sequence (%d), got shape %s" % (msa.shape[0], w.shape))
+    return msa, w, _lib.PlmTripletOpts(-1 if skip_state is None else int(skip_state), int(want))
+
+
+def triplet_stats(msa, q, triplets, weights=None, skip_state=None, counts=False, freq=True, connected=True, device=0):
+    """
+    Three-site statistics of the listed triplets (T x 3, i < j < k) of an alignment (N x L states 0..q-1): a dict with
+    `total` (W, the sum of the fixed-point weights; N for weights=None), `triplets`, and as asked `counts` (T,q,q,q)
+    uint64 -- exact integers --, `freq` = counts / W and `connected` = f_ijk - f_ij f_k - f_ik f_j - f_jk f_i
+    + 2 f_i f_j f_k, both float64.  `weights`: N non-negative floats, quantised to integers as include/plm_hip.h states.
+    """
+    lib = _lib.load()
+    want = (_lib.TRIPLET_COUNTS if counts else 0) | (_lib.TRIPLET_FREQ if freq else 0) | \
+        (_lib.TRIPLET_CONNECTED if connected else 0)
+    msa, w, opts = _triplet_args(msa, weights, skip_state, want)
+    trip = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    shape = (len(trip), q, q, q) if 2 <= q <= 32 else (0,)
+    out = {"triplets": trip,
+           "counts": np.zeros(shape, np.uint64) if counts else None,
+           "freq": np.zeros(shape, np.float64) if freq else None,
+           "connected": np.zeros(shape, np.float64) if connected else None}
+    total = C.c_uint64(0)
+    check(lib.plm_triplet_stats(_ptr(msa), _ptr(w), msa.shape[0], msa.shape[1], int(q), _ptr(trip), len(trip),
+                                C.byref(opts), _ptr(out["counts"]), _ptr(out["freq"]), _ptr(out["connected"]),
+                                C.byref(total), int(device), None))
+    out["total"] = int(total.value)
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def triplet_scan(msa, q, weights=None, sites=None, skip_state=None, device=0, with_total=False):
+    """
+    Connected three-site correlations of every triplet i < j < k among `sites` (strictly ascending; None = all):
+    returns (triplets (T,3) int32 in the order of `triplet_index`, norm2 (T,) = sum C^2, maxabs (T,) = max |C|,
+    argmax_abc (T,3) the states of a cell that attains it), norm2 / maxabs / argmax over the cells that do not involve
+    `skip_state`.  with_total: W is appended.
+    """
+    lib = _lib.load()
+    msa, w, opts = _triplet_args(msa, weights, skip_state, 0)
+    L = msa.shape[1]
+    sel = None if sites is None else np.ascontiguousarray(sites, dtype=np.int32).reshape(-1)
+    n_sel = L if sel is None else len(sel)
+    ascending = sel is None or (len(sel) and (np.diff(sel) > 0).all() and sel[0] >= 0 and sel[-1] < L)
+    T = n_sel * (n_sel - 1) * (n_sel - 2) // 6 if (ascending and 3 <= n_sel <= 2345) else 0
+    norm2, maxabs, arg = np.zeros(T, np.float64), np.zeros(T, np.float64), np.zeros(T, np.int32)
+    total = C.c_uint64(0)
+    check(lib.plm_triplet_scan(_ptr(msa), _ptr(w), msa.shape[0], L, int(q), _ptr(sel), n_sel, C.byref(opts),
+                               _ptr(norm2), _ptr(maxabs), _ptr(arg), C.byref(total), int(device), None))
+    abc = np.stack([arg // (q * q), arg // q % q, arg % q], axis=1).astype(np.int32)
+    out = (triplet_index(L if sel is None else sel), norm2, maxabs, abc)
+    return out + (int(total.value),) if with_total else out
+
+
 def hamiltonians(seqs, q, hi, jij, device=0):
     """
     Statistical energies of sequences under a model: n x 3 float64 (H, H_J, H_h) with

@@ -552,6 +552,47 @@ int plm_cross_identities(const int8_t *a, int32_t n_a, const int8_t *b, int32_t 
 int plm_redundancy_filter(const int8_t *msa, int32_t n_seqs, int32_t n_sites, const plm_ident_opts *opts,
                           uint8_t *keep_out, int32_t *n_kept, int device, void *stream);
 
+/* ---- three-site counts, frequencies and connected correlations of an alignment ---------------------------------------
+ * msa: n_seqs x n_sites int8, row-major, states 0..q-1, 2 <= q <= 32, n_sites >= 3.  weights: n_seqs floats, finite,
+ * >= 0, not all zero; NULL = every weight is 1.  The weights enter as fixed-point integers, computed on the host in
+ * double arithmetic: e = the largest integer <= 30 with max(w) 2^e <= 2^30, wq_n = llrint((double)w_n 2^e) (NULL: wq_n =
+ * 1), W = sum_n wq_n (returned in *total; W = 0, possible when only tiny weights sit next to huge ones, is PLM_EINVAL).
+ * For a triplet i < j < k:
+ *   count_ijk(a,b,c) = sum_n wq_n [x_ni = a, x_nj = b, x_nk = c], an exact integer (u64);
+ *   the lower-order counts are its exact integer marginals (count_ij(a,b) = sum_c count_ijk(a,b,c), ...);
+ *   f = count / W in float64, at every order;
+ *   C_ijk(a,b,c) = f_ijk - f_ij(a,b) f_k(c) - f_ik(a,c) f_j(b) - f_jk(b,c) f_i(a) + 2 f_i(a) f_j(b) f_k(c) in float64;
+ *   norm2 = sum C^2 and maxabs = max |C| over the cells where none of a, b, c equals skip_state (-1: over all cells),
+ *   argmax = a q^2 + b q + c of a cell that attains maxabs.
+ * The counts are accumulated in integers: no output depends on the launch plan, on how the sequences are split over
+ * workgroups or on the order of arrival.  PLM_TRIPLET_PLAN forces the plan (measurements and tests): a comma-separated
+ * list of w32 / w64 (counter width; w32 is refused when W >= 2^32), n<int> (sequences per workgroup of the listed
+ * call), c<int> (c values per counting pass, 1..32), k<int> (workgroups sharing the k range of one (i, j) of the scan,
+ * 1..65535), u (the scan through the kernels of the listed call).
+ * plm_triplet_stats: the listed triplets [T][3] int32, i < j < k (a triplet may be listed twice).  counts [T][q][q][q]
+ *   u64, freq / connected [T][q][q][q] f64; an output is written when its pointer is not NULL and its bit is in want.
+ * plm_triplet_scan: every i < j < k among `sites` (n_sel >= 3 strictly ascending site indices; NULL = all sites, n_sel
+ *   ignored), lexicographic in the positions of the selection: norm2, maxabs [C(n_sel,3)] f64, argmax [C(n_sel,3)]
+ *   int32; any of them may be NULL.
+ * PLM_EINVAL (with a message, before the device is looked at): NULL msa, opts or triplets; n_seqs < 1; n_sites < 3; q
+ * outside 2..32; a state outside 0..q-1; a triplet that is not i < j < k inside 0..n_sites-1; n_triplets < 1; sites not
+ * strictly ascending, out of range, or fewer than 3 (or so many that the triplets pass 2^31 - 1); skip_state outside
+ * -1..q-1; a weight that is negative or not finite; W = 0; a malformed PLM_TRIPLET_PLAN.  PLM_ENOMEM before any
+ * allocation when images plus outputs (T q^3 8 bytes per wanted array of the listed call) do not fit.               */
+#define PLM_TRIPLET_COUNTS 1
+#define PLM_TRIPLET_FREQ 2
+#define PLM_TRIPLET_CONNECTED 4
+typedef struct {
+    int32_t skip_state;   /* -1: none; else 0..q-1, left out of norm2 / maxabs / argmax only */
+    int32_t want;         /* PLM_TRIPLET_COUNTS | _FREQ | _CONNECTED  (listed call)            */
+} plm_triplet_opts;
+int plm_triplet_stats(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
+                      const int32_t *triplets, int32_t n_triplets, const plm_triplet_opts *opts, uint64_t *counts,
+                      double *freq, double *connected, uint64_t *total, int device, void *stream);
+int plm_triplet_scan(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
+                     const int32_t *sites, int32_t n_sel, const plm_triplet_opts *opts, double *norm2, double *maxabs,
+                     int32_t *argmax, uint64_t *total, int device, void *stream);
+
 /* ---- alignment input (host code, no device): what plmc does when it reads the file run_plmc names (tools.py:202-262
  * passes only the path).  evcouplings_amd/alignment_io.py states the rules and keeps a pure-Python twin (fallback and
  * test oracle); these two single passes replace its per-line loop and fancy indexing (0.23 -> 0.03 s at the headline).
