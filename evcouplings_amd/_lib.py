@@ -143,6 +143,29 @@ class PlmTripletOpts(C.Structure):
     _fields_ = [("skip_state", C.c_int32), ("want", C.c_int32)]
 
 
+FIELD_ROLE_STATS, FIELD_ROLE_HESSIAN, FIELD_ROLE_RESIDUAL = 0, 1, 2
+FIELD_HIST, FIELD_MAXBLK = 24, 256
+
+
+class PlmFieldBuffers(C.Structure):
+    _fields_ = [
+        ("gpart", C.c_void_p), ("dpart", C.c_void_p), ("hpart", C.c_void_p), ("hcnt", C.c_void_p), ("hinv", C.c_void_p),
+        ("g2_site", C.c_void_p), ("g2_sum", C.c_void_p), ("h64", C.c_void_p), ("nll_part", C.c_void_p),
+        ("n_gpart", C.c_int64), ("n_hpart", C.c_int64), ("n_hcnt", C.c_int64), ("n_hinv", C.c_int64),
+        ("n_g2_site", C.c_int64), ("n_h64", C.c_int64), ("n_nll_part", C.c_int64),
+    ]
+
+
+class PlmFieldSolve(C.Structure):
+    _fields_ = [
+        ("gh2", C.c_double), ("fx", C.c_double), ("nll", C.c_double),
+        ("passes", C.c_int32), ("done", C.c_int32), ("continuations", C.c_int32),
+        ("final_skip", C.c_int32), ("want_rt", C.c_int32), ("cur", C.c_int32), ("state_passes", C.c_int32),
+        ("c_prev_next", C.c_int32),
+        ("hist", C.c_double * FIELD_HIST), ("quiet", C.c_ubyte * FIELD_MAXBLK),
+    ]
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -213,6 +236,9 @@ SYMBOLS = [
     ("plm_ctx_time_kernels", C.c_int, [_P, C.c_int32, _P]),
     ("plm_ctx_time_field_positions", C.c_int, [_P, C.c_int32, _P]),
     ("plm_ctx_solver_stats", C.c_int, [_P, _P]),
+    ("plm_ctx_field_position", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmFieldBuffers)]),
+    ("plm_ctx_field_solve", C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmFieldSolve), _P,
+                                      C.c_int64]),
     ("plm_rccl_probe", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int, _P]),
     ("plm_rccl_probe_local", C.c_int, [C.c_int32, C.c_int, _P]),
     ("plm_lbfgs_coefficients", None, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P,

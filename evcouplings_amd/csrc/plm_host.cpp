@@ -717,6 +717,24 @@ int fetch_scalars(plm_ctx *c, int first, int count) {
     PLM_HIP(hipStreamSynchronize(c->st));
     return PLM_OK;
 }
+// squared noise floor of the field gradient's f32 sums (PlmOptions::vp_floor; plm_ctx_optimize has the reasoning)
+double ctx_vp_floor2(const plm_ctx *c) {
+    return c->opt.vp_floor * c->opt.vp_floor * c->n_eff * (double)c->d.L * c->d.Q;
+}
+// One variable-projection evaluation from its first launch to its verdict: the evaluation is enqueued, then -- again
+// after every continuation of a chain that ran out of positions -- `fetch` appends the caller's own launches and makes
+// the ONE synchronisation that brings scalar slots 5..7 to the host, and ctx_eval_vp_finish looks at them.
+template <class Fetch>
+int ctx_eval_vp_run(plm_ctx *c, double tol2, Fetch &&fetch, double *gh2_out) {
+    PLM_TRY(ctx_eval_vp_enqueue(c, tol2));
+    for (;;) {
+        PLM_TRY(fetch());
+        bool again = false;
+        PLM_TRY(ctx_eval_vp_finish(c, tol2, &again, gh2_out));
+        if (!again) break;
+    }
+    return PLM_OK;
+}
 
 // scal slots: 0 fx, 1 nll, 2.. dot results
 int dots(plm_ctx *c, int npairs, const float *const *a, const float *const *b, int64_t n, int slot) {
@@ -1448,7 +1466,6 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // it an evaluation only burns passes until the stall test of ctx_eval_vp_finish ends it.
     // (A tolerance relative to the current gradient of the couplings -- inexact field solves far from the optimum --
     // was measured: 0.3 % of |g| costs 15 % more iterations at the headline and stalls config 2 at |g|/|x| = 0.1.)
-    const double vp_floor = c->opt.vp_floor;   // 2e-7 unless a probe set PLM_VP_FLOOR
     // Far from the optimum that absolute tolerance is ~1e-7 of the gradient the fields are solved FOR: the solve may stop
     // at vp_rel (1e-4) of the norm of the reduced gradient at the last accepted point -- the error it leaves in a trial's
     // gradient is of that relative size, far below what a quasi-Newton step notices, and it only binds while
@@ -1461,7 +1478,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // tolerance, so a tolerance of the floor's size would leave |g_h| at that size -- 2e-6 |x| on a small problem, the
     // whole of a tight stop rule; the chain goes below the floor while a pass still gains a factor 2 (k_vp_check).
     const double vp_rel = c->opt.vp_rel;
-    c->vp_floor2 = vp_floor * vp_floor * c->n_eff * (double)d.L * d.Q;
+    c->vp_floor2 = ctx_vp_floor2(c);
     auto vp_tol2 = [&](double xnorm2) {
         const double t = std::max(0.1 * eps * std::max(1.0, std::sqrt(xnorm2)), vp_rel * std::sqrt(gg));
         return t * t;
@@ -1482,11 +1499,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     ctx_set_accurate(c, c->opt.fwd_mode == 1 || (c->opt.fwd_mode != 0 && resume && c->eval_accurate));
     auto start_eval = [&](bool have) -> int {
         const double tol2 = vp_tol2((double)d.L);
-        if (!have) {
-            if (!vp) PLM_TRY(ctx_eval_enqueue(c));
-            else PLM_TRY(ctx_eval_vp_enqueue(c, tol2));
-        }
-        for (;;) {
+        auto fetch = [&]() -> int {      // the norms the first direction needs, with the evaluation's scalars
             PlmVecList Qg, Bg;
             Qg.n = 1; Qg.v[0] = c->g;
             Bg.n = 2; Bg.v[0] = c->g; Bg.v[1] = c->g;
@@ -1494,9 +1507,13 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             PLM_TRY(norm_dots());
             PLM_TRY(ctx_allreduce_scalars(c, have ? SL_DG : 0, (have ? 8 - SL_DG : 8) + 2));
             PLM_TRY(fetch_scalars(c, 0, 10));
-            bool again = false;
-            if (vp && !have) PLM_TRY(ctx_eval_vp_finish(c, tol2, &again, &gh2));
-            if (!again) break;
+            return PLM_OK;
+        };
+        if (vp && !have) {
+            PLM_TRY(ctx_eval_vp_run(c, tol2, fetch, &gh2));
+        } else {
+            if (!have) PLM_TRY(ctx_eval_enqueue(c));
+            PLM_TRY(fetch());
         }
         gDg = c->h_scal[SL_MD];
         gg = c->h_scal[SL_MD + 1];
@@ -1908,6 +1925,104 @@ int plm_ctx_time_field_positions(plm_ctx_t *c, int32_t reps, float *out_ms) {
     out_ms[0] = (float)(acc[0] / reps);
     out_ms[1] = (float)(acc[1] / reps);
     return rc;
+}
+
+// ---- the field solver, test-facing (include/plm_hip.h: diagnostic) ----------------------------------------------
+static int field_probe_checks(plm_ctx_t *c) {
+    if (!c->have_weights) return fail(PLM_EINVAL, "weights not set");
+    if (c->d.nshards != 1 || c->d.sharded) return fail(PLM_EUNSUPPORTED, "the field-solver probes run on single-shard contexts");
+    if (!vp_enabled(c)) return fail(PLM_EINVAL, "the field-solver probes need a variable-projection context (not joint, lambda_h > 0)");
+    return PLM_OK;
+}
+int plm_ctx_field_position(plm_ctx_t *c, int32_t role, int32_t accurate, int32_t update, int32_t prefill,
+                           plm_field_buffers_t *out) {
+    if (!c || !out) return fail(PLM_EINVAL, "NULL argument");
+    if (role < PLM_FIELD_ROLE_STATS || role > PLM_FIELD_ROLE_RESIDUAL) return fail(PLM_EINVAL, "unknown role %d", (int)role);
+    if (!out->gpart || !out->dpart || !out->hpart || !out->hcnt || !out->hinv || !out->g2_site || !out->g2_sum || !out->h64 ||
+        !out->nll_part)
+        return fail(PLM_EINVAL, "NULL output buffer");
+    PLM_TRY(field_probe_checks(c));
+    const PlmDims &d = c->d;
+    const int64_t nsites = (int64_t)(d.b16_hi - d.b16_lo) * 16, hs = (int64_t)plm_h64_stride(d);
+    const int64_t n_g = (int64_t)(plm_gpart_bytes(d) / sizeof(double)), n_h = (int64_t)(plm_hpart_bytes(d) / sizeof(float));
+    if (out->n_gpart != n_g || out->n_hpart != n_h || out->n_hcnt != hs || out->n_hinv != nsites * d.Q * d.Q ||
+        out->n_g2_site != nsites || out->n_h64 != 2 * hs || out->n_nll_part != c->n_fx_part())
+        return fail(PLM_EINVAL, "output buffer sizes do not match the context");
+    PLM_HIP(hipSetDevice(c->device));
+    PLM_TRY(vp_alloc(c));
+    const int full = role == PLM_FIELD_ROLE_HESSIAN ? 1 : 0;
+    if (!full && update && c->vp_hess_age < 0) return fail(PLM_EINVAL, "no cached inverse Hessians: run a Hessian position first");
+    c->eval_valid = false;
+    ctx_set_accurate(c, accurate != 0);
+    PLM_TRY(vp_stage1(c));
+    if (prefill) {
+        PLM_HIP(hipMemsetAsync(c->gpart, 0xFF, plm_gpart_bytes(d), c->st));
+        PLM_HIP(hipMemsetAsync(c->dpart, 0xFF, plm_gpart_bytes(d), c->st));
+        PLM_HIP(hipMemsetAsync(c->hpart, 0xFF, plm_hpart_bytes(d), c->st));
+        PLM_HIP(hipMemsetAsync(c->fx_part, 0xFF, sizeof(double) * c->n_fx_part(), c->st));
+        PLM_HIP(hipMemsetAsync(c->h64 + hs, 0xFF, sizeof(double) * hs, c->st));
+    }
+    // the launches of a chain position (vp_chain), without chain state
+    if (role == PLM_FIELD_ROLE_RESIDUAL)
+        PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 1, c->fwd_accurate, c->Rt, c->fx_part, c->hpart, c->gpart,
+                                 nullptr, nullptr, PLM_VP_ALWAYS, c->st));
+    else
+        PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 0, full ? 2 : 1, c->fwd_accurate, nullptr, nullptr, c->hpart,
+                                 c->gpart, c->dpart, nullptr, PLM_VP_ALWAYS, c->st));
+    PLM_HIP(plm_launch_hsolve(d, c->hpart, c->gpart, full, c->x, c->h64, c->prob.lambda_h, update ? 1 : 0, c->hinv, c->hg2,
+                              c->scal + 5, 0.0, 0.0, nullptr, 0, c->hcnt, c->dpart, c->st));
+    if (full) c->vp_hess_age = 0;
+    PLM_HIP(hipMemcpyAsync(out->gpart, c->gpart, sizeof(double) * n_g, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->dpart, c->dpart, sizeof(double) * n_g, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->hpart, c->hpart, sizeof(float) * n_h, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->hcnt, c->hcnt, sizeof(double) * hs, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->hinv, c->hinv, sizeof(double) * nsites * d.Q * d.Q, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->g2_site, c->hg2, sizeof(double) * nsites, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->g2_sum, c->scal + 5, sizeof(double), hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->h64, c->h64, sizeof(double) * 2 * hs, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipMemcpyAsync(out->nll_part, c->fx_part, sizeof(double) * c->n_fx_part(), hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
+    return PLM_OK;
+}
+int plm_ctx_field_solve(plm_ctx_t *c, double tol, int32_t vp_c_prev, int32_t invalidate, int32_t accurate,
+                        plm_field_solve_t *res, double *fields, int64_t n_fields) {
+    if (!c || !res || !fields) return fail(PLM_EINVAL, "NULL argument");
+    if (!(tol >= 0) || vp_c_prev < 0 || vp_c_prev > 11) return fail(PLM_EINVAL, "tol must be >= 0 and vp_c_prev in 0..11");
+    PLM_TRY(field_probe_checks(c));
+    const PlmDims &d = c->d;
+    const int64_t hs = (int64_t)plm_h64_stride(d);
+    if (n_fields != hs) return fail(PLM_EINVAL, "fields must hold %lld doubles", (long long)hs);
+    static_assert(PLM_FIELD_HIST == PLM_VP_HIST && PLM_FIELD_MAXBLK == PLM_VP_MAXBLK, "plm_field_solve_t mirrors PlmVpState");
+    PLM_HIP(hipSetDevice(c->device));
+    PLM_TRY(vp_alloc(c));
+    c->eval_valid = false;
+    ctx_set_accurate(c, accurate != 0);
+    c->vp_floor2 = ctx_vp_floor2(c);
+    c->vp_c_prev = vp_c_prev;
+    if (invalidate) c->vp_hess_age = -1;
+    const double tol2 = tol * tol;
+    double gh2 = 0;
+    PLM_TRY(ctx_eval_vp_run(c, tol2, [&]() -> int { return fetch_scalars(c, 0, 8); }, &gh2));
+    PlmVpState S;
+    PLM_HIP(hipMemcpyAsync(&S, c->vp_flag, sizeof S, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
+    PLM_HIP(hipMemcpyAsync(fields, c->h64 + (size_t)(S.cur ? hs : 0), sizeof(double) * hs, hipMemcpyDeviceToHost, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));
+    memset(res, 0, sizeof *res);
+    res->gh2 = gh2;
+    res->fx = c->h_scal[0];
+    res->nll = c->h_scal[1];
+    res->passes = (int32_t)std::lround(c->h_scal[6]);
+    res->done = c->h_scal[7] > 0.5 ? 1 : 0;
+    res->continuations = c->vp_extra;
+    res->final_skip = S.final_skip;
+    res->want_rt = S.want_rt;
+    res->cur = S.cur;
+    res->state_passes = S.passes;
+    res->c_prev_next = c->vp_c_prev;
+    memcpy(res->hist, S.hist, sizeof res->hist);
+    memcpy(res->quiet, S.quiet, sizeof res->quiet);
+    return PLM_OK;
 }
 
 int plm_ctx_time_kernels(plm_ctx_t *c, int32_t reps, float *out_ms) {

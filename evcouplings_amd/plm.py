@@ -1059,6 +1059,43 @@ class PlmContext:
                 # the two GEMMs as the fit ran them (HIP events inside the fit; plain arithmetic only)
                 "gemm_evaluations": int(out[4]), "forward_ms_per_evaluation": out[5] / gv, "backward_ms_per_evaluation": out[6] / gv}
 
+    # ---- the field solver, test-facing (diagnostic: tests/test_gpu_field_solver.py) ----
+    def field_dims(self):
+        """Q (the instantiated alphabet), sequence tiles of 256, 16-site blocks: the shapes of the solver's raw buffers"""
+        q = self.q
+        Q = 4 if q <= 4 else 5 if q == 5 else 20 if q <= 20 else 21 if q == 21 else 32
+        return Q, (self.N + 255) // 256, (self.L + 15) // 16
+
+    def field_position(self, role, accurate=False, update=True, prefill=False):
+        """plm_ctx_field_position: one unchained position of the field solver at the current x in the role "stats",
+        "hessian" or "residual"; the device buffers as they are (arrays in the Q-state layout of field_dims)"""
+        Q, T, B = self.field_dims()
+        S, NH = 16 * B, Q * (Q + 1) // 2
+        out = dict(gpart=np.zeros((B, T, 16, Q)), dpart=np.zeros((B, T, 16, Q)), hpart=np.zeros((B, T, 16, NH), np.float32),
+                   hcnt=np.zeros((S, Q)), hinv=np.zeros((S, Q, Q)), g2_site=np.zeros(S), g2_sum=np.zeros(1),
+                   h64=np.zeros((2, S, Q)), nll_part=np.zeros((B, T)))
+        buf = _lib.PlmFieldBuffers()
+        for k, v in out.items():
+            setattr(buf, k, v.ctypes.data)
+        buf.n_gpart, buf.n_hpart, buf.n_hcnt, buf.n_hinv = out["gpart"].size, out["hpart"].size, out["hcnt"].size, out["hinv"].size
+        buf.n_g2_site, buf.n_h64, buf.n_nll_part = S, out["h64"].size, out["nll_part"].size
+        role = {"stats": _lib.FIELD_ROLE_STATS, "hessian": _lib.FIELD_ROLE_HESSIAN, "residual": _lib.FIELD_ROLE_RESIDUAL}[role]
+        check(self.lib.plm_ctx_field_position(self._h, role, int(bool(accurate)), int(bool(update)), int(bool(prefill)),
+                                              C.byref(buf)))
+        return out
+
+    def field_solve(self, tol, vp_c_prev=3, invalidate=False, accurate=False):
+        """plm_ctx_field_solve: the field solver's chain of one variable-projection evaluation at the current x"""
+        Q, T, B = self.field_dims()
+        fields = np.zeros((16 * B, Q))
+        res = _lib.PlmFieldSolve()
+        check(self.lib.plm_ctx_field_solve(self._h, float(tol), int(vp_c_prev), int(bool(invalidate)), int(bool(accurate)),
+                                           C.byref(res), _ptr(fields), fields.size))
+        return dict(gh2=res.gh2, fx=res.fx, nll=res.nll, passes=res.passes, done=bool(res.done),
+                    continuations=res.continuations, final_skip=res.final_skip, want_rt=res.want_rt, cur=res.cur,
+                    state_passes=res.state_passes, c_prev_next=res.c_prev_next, hist=np.array(res.hist[:]),
+                    quiet=np.array(res.quiet[:], np.uint8), fields=fields)
+
     def time_field_positions(self, reps=5):
         """ms of one Hessian position and of the closing (residual-writing) position of the field solver's chain on this
         context's site blocks (plm_ctx_time_field_positions; call time_kernels first)"""

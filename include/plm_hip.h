@@ -666,6 +666,53 @@ int plm_ctx_time_field_positions(plm_ctx_t *ctx, int32_t reps, float *out_ms /* 
 #define PLM_S_COUNT 7
 int plm_ctx_solver_stats(plm_ctx_t *ctx, double *out /* [PLM_S_COUNT] */);
 
+/* -- field solver, test-facing (DIAGNOSTIC: tests/test_gpu_field_solver.py; no product path calls these) -------------
+ * Both run on a single-shard context (PLM_EUNSUPPORTED otherwise) whose fit uses variable projection (PLM_EINVAL for a
+ * joint-L-BFGS context or lambda_h = 0), with weights set, in the arithmetic the caller names (accurate = 0: plain, 1:
+ * the accurate evaluation's) -- the environment switch is read once at context creation.  Sizes below: Q = the
+ * instantiated alphabet (4 / 5 / 20 / 21 / 32), T = sequence tiles of 256, B = 16-site blocks, S = 16 B sites.
+ *
+ * plm_ctx_field_position: ONE unchained position of the solver at the context's current x.  Stage 1 (expand, forward
+ * GEMM into the stored potentials, f64 fields <- x), one pass in the role asked for, then the per-site Newton step
+ * without chain state (in place, on field buffer 0), with fresh inverses exactly when the pass carried Hessian sums
+ * (PLM_FIELD_ROLE_HESSIAN); the other roles step with the inverses cached by an earlier Hessian position on this
+ * context (PLM_EINVAL if update is asked for and none exists).  update = 0: norms only, no field moves.  prefill != 0:
+ * the partial-sum buffers, the -log P partials and field buffer 1 are filled with 0xFF bytes (NaN) before the pass, so
+ * the caller sees what a launch did not write.  The device buffers come back RAW -- no reduction on the host:
+ *   gpart, dpart [B][T][16][Q] f64; hpart [B][T][16][Q (Q + 1) / 2] f32; hcnt [S][Q]; hinv [S][Q][Q]; g2_site [S];
+ *   g2_sum [1]; h64 [2][S][Q] (both field buffers); nll_part [B][T] (-log P partials: written by the residual role).
+ * Every pointer must be non-NULL and every n_* the element count above (PLM_EINVAL). */
+#define PLM_FIELD_ROLE_STATS 0      /* statistics pass: gradient sums */
+#define PLM_FIELD_ROLE_HESSIAN 1    /* Hessian position: + diagonal sums, + Hessian sums on every 32nd tile */
+#define PLM_FIELD_ROLE_RESIDUAL 2   /* residual-writing pass: gradient sums, residual planes, -log P partials */
+typedef struct {
+    double *gpart, *dpart;
+    float *hpart;
+    double *hcnt, *hinv, *g2_site, *g2_sum, *h64, *nll_part;
+    int64_t n_gpart, n_hpart, n_hcnt, n_hinv, n_g2_site, n_h64, n_nll_part;   /* n_gpart counts gpart and dpart each */
+} plm_field_buffers_t;
+int plm_ctx_field_position(plm_ctx_t *ctx, int32_t role, int32_t accurate, int32_t update, int32_t prefill,
+                           plm_field_buffers_t *out);
+/* plm_ctx_field_solve: the field solver's chain as a variable-projection evaluation of plm_ctx_optimize runs it at the
+ * current x (enqueue, one synchronisation, verdict; repeated while the chain ran out of positions), with the squared
+ * tolerance tol^2, the pass count of the "previous evaluation" vp_c_prev (0..11) and, invalidate != 0, no cached
+ * inverses.  Afterwards plm_ctx_get_x / plm_ctx_get_g hold the evaluation's point (fields solved) and reduced gradient.
+ * fields [S][Q]: the chain's current f64 fields (n_fields = S Q). */
+#define PLM_FIELD_HIST 24
+#define PLM_FIELD_MAXBLK 256
+typedef struct {
+    double gh2;                 /* squared field-gradient norm the evaluation reports */
+    double fx, nll;             /* objective and its -log P part at the returned point */
+    int32_t passes, done;       /* the verdict slots as the host read them last */
+    int32_t continuations;      /* times the host continued a chain that ran out of positions */
+    int32_t final_skip, want_rt, cur, state_passes;   /* the device-side chain state at the end */
+    int32_t c_prev_next;        /* the pass count the next evaluation would be planned with */
+    double hist[PLM_FIELD_HIST];              /* per pass: squared norm + 1e9 x open sites */
+    unsigned char quiet[PLM_FIELD_MAXBLK];    /* 16-site blocks that stopped moving */
+} plm_field_solve_t;
+int plm_ctx_field_solve(plm_ctx_t *ctx, double tol, int32_t vp_c_prev, int32_t invalidate, int32_t accurate,
+                        plm_field_solve_t *result, double *fields, int64_t n_fields);
+
 /* -- host arithmetic exposed for tests (no device) ------------------------------------------ */
 /* Two-loop recursion of L-BFGS in coefficient space over a ring of m history slots, of which the `stored` slots
  * before `end` (ring order, newest = end - 1) are live: direction p = sum_j cs[j] s_j + D^-1 (sum_j cy[j] y_j + cg g).
