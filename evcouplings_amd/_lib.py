@@ -128,6 +128,27 @@ class PlmPtResult(C.Structure):
 
 PT_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
 
+
+class PlmAnnealOpts(C.Structure):
+    _fields_ = [
+        ("n_chains", C.c_int32), ("n_steps", C.c_int32), ("sweeps_per_step", C.c_int32), ("max_greedy", C.c_int32),
+        ("first_sweep", C.c_uint32), ("steps_per_launch", C.c_int32),
+        ("betas", C.c_void_p), ("seed", C.c_uint64),
+        ("start", C.c_void_p), ("fixed", C.c_void_p), ("allowed", C.c_void_p),
+    ]
+
+
+class PlmAnnealResult(C.Structure):
+    _fields_ = [
+        ("states", C.c_void_p), ("gain", C.c_void_p), ("best", C.c_void_p), ("best_gain", C.c_void_p),
+        ("best_at", C.c_void_p), ("last_move", C.c_void_p), ("converged", C.c_void_p),
+        ("energies", C.c_void_p), ("best_energies", C.c_void_p),
+        ("steps_done", C.c_int32), ("status", C.c_int32),
+    ]
+
+
+ANNEAL_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
+
 IDENT_DENOM = {"columns": 0, "both": 1, "shorter": 2}
 
 
@@ -203,6 +224,8 @@ SYMBOLS = [
                           C.POINTER(PlmAisResult)]),
     ("plm_pt", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmPtOpts), C.c_int, _P, PT_CB, _P,
                          C.POINTER(PlmPtResult)]),
+    ("plm_anneal", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmAnnealOpts), C.c_int, _P, ANNEAL_CB, _P,
+                             C.POINTER(PlmAnnealResult)]),
     ("plm_meanfield", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int, _P,
                                 C.POINTER(PlmMfResult)]),
     ("plm_direct_information", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int, _P, _P]),

@@ -105,17 +105,6 @@ hipError_t launch_steps(const gibbs::SweepPlan &p, hipStream_t st, const AisArgs
         });
 }
 
-// Steps per launch that keep a launch near a second: a workgroup of the tiled form spends about 150 ns per pair of sites
-// at q = 21 (13 ms per sweep of 300 sites, section 9.6), in proportion to the row width; the workgroups beyond one per CU
-// queue; the direct form is taken as eight times slower.  An estimate: the result does not depend on it.
-int default_steps_per_launch(const gibbs::SweepPlan &p, int L, int C, int n_per, int K, int n_cu) {
-    const double rounds = std::ceil((double)((C + p.tile - 1) / p.tile) / std::max(n_cu, 1));
-    double per_step = (double)n_per * rounds * (double)L * L * 150e-9 * p.NV / 6.0;
-    if (p.direct) per_step *= 8.0;
-    const double steps = 1.0 / std::max(per_step, 1e-9);
-    return steps >= (double)K ? K : std::max(1, (int)steps);
-}
-
 }  // namespace
 
 int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_ais_opts *opts, int device,
@@ -147,7 +136,7 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
     int n_cu = 0;
     PLM_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
     const int per_launch = opts->steps_per_launch > 0 ? std::min(opts->steps_per_launch, K)
-                                                      : default_steps_per_launch(plan, L, C, n, K, n_cu);
+                                                      : gibbs::default_steps_per_launch(plan, L, C, n, K, n_cu);
 
     // log Z_0 = sum_i log sum_a exp h_i(a) in float64
     double log_z0 = 0.0;

@@ -349,6 +349,47 @@ hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, in
         });
 }
 
+// Steps per launch that keep a launch near a second: a workgroup of the tiled form spends about 150 ns per pair of sites
+// at q = 21 (13 ms per sweep of 300 sites, section 9.6), in proportion to the row width; the workgroups beyond one per CU
+// queue; the direct form is taken as eight times slower.  An estimate: no result depends on it.
+int default_steps_per_launch(const SweepPlan &p, int L, int C, int n_per, int K, int n_cu) {
+    const double rounds = std::ceil((double)((C + p.tile - 1) / p.tile) / std::max(n_cu, 1));
+    double per_step = (double)n_per * rounds * (double)L * L * 150e-9 * p.NV / 6.0;
+    if (p.direct) per_step *= 8.0;
+    const double steps = 1.0 / std::max(per_step, 1e-9);
+    return steps >= (double)K ? K : std::max(1, (int)steps);
+}
+
+int state_energies(const int8_t *rows, size_t n_rows, int L, int q, const float *x_canonical, int device, void *stream,
+                   double *energies_out) {
+    if (L == 1) {
+        hipStream_t st = (hipStream_t)stream;
+        float *h = nullptr;
+        int8_t *x = nullptr;
+        double *en = nullptr;
+        DeviceBuffers mem;
+        PLM_TRY(mem.alloc(&h, (size_t)q));
+        PLM_TRY(mem.alloc(&x, n_rows));
+        PLM_TRY(mem.alloc(&en, n_rows * 3));
+        PLM_HIP(hipMemcpyAsync(h, x_canonical, (size_t)q * sizeof(float), hipMemcpyHostToDevice, st));
+        PLM_HIP(hipMemcpyAsync(x, rows, n_rows, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_field_energy, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, h, x, (int64_t)n_rows, en);
+        PLM_HIP(hipGetLastError());
+        PLM_HIP(hipMemcpyAsync(energies_out, en, n_rows * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        PLM_HIP(hipStreamSynchronize(st));
+        return PLM_OK;
+    }
+    // the code path of plm_hamiltonians, in row chunks that stay inside its limit on sequences per call
+    const size_t Lp = ((size_t)L + 31) / 32 * 32;
+    const size_t max_rows = std::max<size_t>(256, (((size_t)1 << 30) / Lp) / 256 * 256);
+    int rc = PLM_OK;
+    for (size_t r0 = 0; r0 < n_rows && rc == PLM_OK; r0 += max_rows) {
+        const size_t n = std::min(max_rows, n_rows - r0);
+        rc = plm_hamiltonians(rows + r0 * L, (int32_t)n, L, q, x_canonical, device, stream, energies_out + r0 * 3);
+    }
+    return rc;
+}
+
 }  // namespace gibbs
 
 int plm_sample_plan(int32_t n_sites, int32_t n_states, int32_t n_chains, int32_t n_cu, plm_sample_plan_info *out) {
@@ -440,18 +481,8 @@ int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
     }
     PLM_HIP(hipStreamSynchronize(st));
     mem.free_all();                          // before plm_hamiltonians allocates its own
-    int rc = PLM_OK;
-    if (energies_out && L > 1) {
-        // the statistical energies of the snapshots at beta = 1: the code path of plm_hamiltonians, in row chunks that
-        // stay inside its limit on sequences per call
-        const size_t Lp = ((size_t)L + 31) / 32 * 32;
-        const size_t max_rows = std::max<size_t>(256, (((size_t)1 << 30) / Lp) / 256 * 256);
-        const size_t rows = (size_t)C * (size_t)K;
-        for (size_t r0 = 0; r0 < rows && rc == PLM_OK; r0 += max_rows) {
-            const size_t n = std::min(max_rows, rows - r0);
-            rc = plm_hamiltonians(samples_out + r0 * L, (int32_t)n, L, q, x_canonical, device, stream,
-                                  energies_out + r0 * 3);
-        }
-    }
-    return rc;
+    // the statistical energies of the snapshots at beta = 1
+    if (energies_out && L > 1)
+        return gibbs::state_energies(samples_out, (size_t)C * (size_t)K, L, q, x_canonical, device, stream, energies_out);
+    return PLM_OK;
 }

@@ -1,6 +1,7 @@
-// plm_sample_internal.h -- what plm_sample.hip shares with plm_ais.hip, plm_pt.hip and plm_bm.hip: the checks the four
-// entry points (plm_sample, plm_ais, plm_pt, plm_bm_fit) open with, the plan, the expansion of the couplings, the sweep
-// launchers, and the step from a plan to the template arguments of a sweep kernel.
+// plm_sample_internal.h -- what plm_sample.hip shares with plm_ais.hip, plm_pt.hip, plm_anneal.hip and plm_bm.hip: the
+// checks the five entry points (plm_sample, plm_ais, plm_pt, plm_anneal, plm_bm_fit) open with, the plan, the expansion of
+// the couplings, the sweep launchers, the energies of the states returned, and the step from a plan to the template
+// arguments of a sweep kernel.
 #pragma once
 #include "plm_host_util.h"
 #include <type_traits>
@@ -34,6 +35,15 @@ hipError_t expand(hipStream_t st, const float *canon, int L, int q, float4 *W);
 hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
                   const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
                   int8_t *dst);
+
+// steps of n_per sweeps per launch, out of K, that keep a launch of plm_ais or plm_anneal near a second (an estimate)
+int default_steps_per_launch(const SweepPlan &p, int L, int C, int n_per, int K, int n_cu);
+
+// (H, H_J, H_h) of n_rows host rows of L states into energies_out [n_rows][3]: what plm_hamiltonians returns for them,
+// and the field-only model (L == 1), which its forward GEMM cannot take.  Allocates: call it after the caller's buffers
+// are freed.
+int state_energies(const int8_t *rows, size_t n_rows, int L, int q, const float *x_canonical, int device, void *stream,
+                   double *energies_out);
 
 // ---- from a plan to a kernel ----
 template <int V> using Int = std::integral_constant<int, V>;

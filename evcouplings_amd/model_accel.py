@@ -18,6 +18,8 @@ DESIGN_NEXT_ROWS.md section 9.6); the reference has no sampler, so `install()` h
 Boltzmann-machine loop (`plm_bm_fit`, section 9.7), so that its samples reproduce those frequencies.
 `log_partition(model)` estimates log Z by annealed importance sampling (`plm_ais`, section 9.8), and
 `log_probabilities(model, sequences, log_z)` turns statistical energies into log-probabilities with it.
+`optimize_sequences(model, n)` searches a model for its highest-scoring sequences by simulated annealing and greedy
+ascent (`plm_anneal`, section 9.13), and `local_optima(model, sequences)` climbs from given sequences.
 """
 from copy import deepcopy
 
@@ -66,42 +68,68 @@ def sample_sequences(model, n_chains, burn_in=100, n_snapshots=1, thin=1, beta=1
     from evcouplings_amd import plm
     h_i = np.asarray(model.h_i)
     L, q = h_i.shape
-    letters = np.array(list(model.alphabet) if isinstance(model.alphabet, str) else model.alphabet).astype("U1")
-    if len(letters) != q:
-        raise ValueError("the model's alphabet has %d letters, its fields %d states" % (len(letters), q))
-    code = {a: k for k, a in enumerate(letters)}
+    letters, x0, flags, allowed = _chain_setup(model, n_chains, start, fixed, exclude, beta, seed, device)
+    out, en = plm.sample(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_chains, burn_in=burn_in,
+                         n_snapshots=n_snapshots, thin=thin, beta=beta, seed=seed, start=x0, fixed=flags, allowed=allowed,
+                         energies=energies, device=device)
+    out = out.reshape(-1, L)
+    res = letters[out] if as_letters else out
+    return (res, en.reshape(-1, 3)) if energies else res
 
-    def states(mat):
-        mat = np.asarray(mat)
-        if mat.dtype.kind in "iu":
-            return mat.astype(np.int8)
-        try:
-            return np.vectorize(code.__getitem__, otypes=[np.int8])(mat.astype("U1"))
-        except KeyError as e:
-            raise ValueError("letter %s is not in the model's alphabet" % e)
 
-    target = states(np.array(list(model.target_seq)))
-    allowed = None
-    if exclude:
-        unknown = [a for a in exclude if a not in code]
-        if unknown:
-            raise ValueError("excluded letters %r are not in the model's alphabet" % "".join(unknown))
-        allowed = np.ones(q, np.uint8)
-        allowed[[code[a] for a in exclude]] = 0
-    flags = None
-    if fixed is not None and len(fixed):
-        pos = {int(p): k for k, p in enumerate(np.asarray(model.index_list))}
-        missing = [p for p in fixed if int(p) not in pos]
-        if missing:
-            raise ValueError("positions %r are not in the model's index_list" % missing)
-        flags = np.zeros(L, np.uint8)
-        flags[[pos[int(p)] for p in fixed]] = 1
+def _to_states(mat, code):
+    """A matrix of letters, or of states already, as int8 states."""
+    mat = np.asarray(mat)
+    if mat.dtype.kind in "iu":
+        return mat.astype(np.int8)
+    try:
+        return np.vectorize(code.__getitem__, otypes=[np.int8])(mat.astype("U1"))
+    except KeyError as e:
+        raise ValueError("letter %s is not in the model's alphabet" % e)
+
+
+def _site_flags(model, fixed, L):
+    """Positions in the model's own numbering (`index_list`) as L flags, or None when there are none."""
+    if fixed is None or not len(fixed):
+        return None
+    pos = {int(p): k for k, p in enumerate(np.asarray(model.index_list))}
+    missing = [p for p in fixed if int(p) not in pos]
+    if missing:
+        raise ValueError("positions %r are not in the model's index_list" % missing)
+    flags = np.zeros(L, np.uint8)
+    flags[[pos[int(p)] for p in fixed]] = 1
+    return flags
+
+
+def _allowed_flags(exclude, code, q):
+    """The q flags of the states that may be drawn when the letters of `exclude` may not, or None."""
+    if not exclude:
+        return None
+    unknown = [a for a in exclude if a not in code]
+    if unknown:
+        raise ValueError("excluded letters %r are not in the model's alphabet" % "".join(unknown))
+    allowed = np.ones(q, np.uint8)
+    allowed[[code[a] for a in exclude]] = 0
+    return allowed
+
+
+def _chain_setup(model, n_chains, start, fixed, exclude, beta, seed, device):
+    """What `sample_sequences` and `optimize_sequences` make of their arguments: (the alphabet as an array of letters, the
+    start states or None for the start rule, the flags of the fixed sites or None, the flags of the allowed states or
+    None).  Fixed sites hold the target's residue in the start states."""
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    letters, code = _letters_and_code(model, q)
+    target = _to_states(np.array(list(model.target_seq)), code)
+    allowed = _allowed_flags(exclude, code, q)
+    flags = _site_flags(model, fixed, L)
     if isinstance(start, str):
         if start != "target":
             raise ValueError('start must be None, "target" or a matrix')
         x0 = np.tile(target, (int(n_chains), 1))
     elif start is not None:
-        x0 = states(start).reshape(int(n_chains), L).copy()
+        x0 = _to_states(start, code).reshape(int(n_chains), L).copy()
     elif flags is not None:
         # the start rule knows no fixed sites: draw it, then put the target's residues there
         x0 = plm.sample(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_chains, burn_in=0, beta=beta, seed=seed,
@@ -110,12 +138,64 @@ def sample_sequences(model, n_chains, burn_in=100, n_snapshots=1, thin=1, beta=1
         x0 = None
     if flags is not None:
         x0[:, flags.astype(bool)] = target[flags.astype(bool)]
-    out, en = plm.sample(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_chains, burn_in=burn_in,
-                         n_snapshots=n_snapshots, thin=thin, beta=beta, seed=seed, start=x0, fixed=flags, allowed=allowed,
-                         energies=energies, device=device)
-    out = out.reshape(-1, L)
-    res = letters[out] if as_letters else out
-    return (res, en.reshape(-1, 3)) if energies else res
+    return letters, x0, flags, allowed
+
+
+def optimize_sequences(model, n_chains, betas=None, n_steps=100, sweeps_per_step=1, max_greedy=100, seed=0, start=None,
+                       fixed=None, exclude="", top=None, as_letters=True, info=False, device=0):
+    """
+    Search a `CouplingsModel` (as for `sample_sequences`) for sequences of high statistical energy H by simulated
+    annealing and greedy ascent (`plm.anneal`, DESIGN_NEXT_ROWS.md section 9.13): n_chains chains make sweeps_per_step
+    Gibbs sweeps at every inverse temperature of betas (None: `plm.annealing_schedule(n_steps)`), then at most max_greedy
+    greedy sweeps; every chain reports the best state it held at a checkpoint.  start, fixed and exclude mean what they
+    mean in `sample_sequences` ("target": every chain starts from the target sequence; fixed positions, in `index_list`
+    numbering, keep the target's residue; excluded letters are never proposed).
+    Returns (sequences, energies, chains): the distinct best sequences as an (M, L) matrix of letters (as_letters) or of
+    int8 states, sorted by H descending (the first chain's on equal H) and cut to `top` rows; their (M, 3) energies
+    (H, H_J, H_h); and how many chains ended in each.  With info=True the dict of `plm.anneal` follows.
+    """
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    letters, x0, flags, allowed = _chain_setup(model, n_chains, start, fixed, exclude, 1.0, seed, device)
+    res = plm.anneal(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, n_chains, betas=betas, n_steps=n_steps,
+                     sweeps_per_step=sweeps_per_step, max_greedy=max_greedy, seed=seed, start=x0, fixed=flags,
+                     allowed=allowed, device=device)
+    best, en = np.asarray(res["best"]), np.asarray(res["best_energies"])
+    _, first, counts = np.unique(best, axis=0, return_index=True, return_counts=True)
+    order = sorted(range(len(first)), key=lambda u: (-en[first[u], 0], first[u]))[:top]
+    rows = first[order]
+    out = best[rows]
+    ret = (letters[out.astype(np.int64)] if as_letters else out, en[rows], counts[order])
+    return ret + (res,) if info else ret
+
+
+def local_optima(model, sequences, fixed=None, exclude="", max_sweeps=100, as_letters=True, info=False, device=0):
+    """
+    The local optimum of H every given sequence runs into under single-site moves (`plm.greedy_ascent`): greedy sweeps
+    from each row of `sequences` (an (N, L) matrix of letters of the model's alphabet or of states, or a list of strings;
+    for example the natural alignment) until a sweep moves nothing.  Fixed positions (`index_list` numbering) keep the
+    residue of the given sequence; excluded letters are never moved to, and a sequence that holds one at a free position
+    is refused.
+    Returns (optima, energies, mutations, last_move): the (N, L) optima, their (N, 3) energies (H, H_J, H_h), the number
+    of positions at which an optimum differs from its start, and the number of the last sweep that moved something (0:
+    the sequence is a local optimum itself).  With info=True the dict of `plm.anneal` follows.
+    """
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    letters, code = _letters_and_code(model, q)
+    if len(sequences) and isinstance(sequences[0], str):
+        sequences = [list(s) for s in sequences]
+    x0 = _to_states(sequences, code)
+    if x0.ndim != 2 or x0.shape[1] != L:
+        raise ValueError("sequences must have the model's %d positions" % L)
+    res = plm.greedy_ascent(h_i, _pairs_from_dense(np.asarray(model.J_ij)), q, x0, max_sweeps=max_sweeps,
+                            fixed=_site_flags(model, fixed, L), allowed=_allowed_flags(exclude, code, q), device=device)
+    out = np.asarray(res["states"])
+    ret = (letters[out.astype(np.int64)] if as_letters else out, res["energies"], (out != x0).sum(axis=1),
+           res["last_move"])
+    return ret + (res,) if info else ret
 
 
 def sample_tempered(model, n_ladders, betas=None, n_rungs=8, beta_max=1.0, burn_in=100, n_snapshots=1, thin=1,
@@ -142,13 +222,7 @@ def sample_tempered(model, n_ladders, betas=None, n_rungs=8, beta_max=1.0, burn_
     betas = np.asarray(betas, np.float32).reshape(-1)
 
     def states(mat):
-        mat = np.asarray(mat)
-        if mat.dtype.kind in "iu":
-            return mat.astype(np.int8)
-        try:
-            return np.vectorize(code.__getitem__, otypes=[np.int8])(mat.astype("U1"))
-        except KeyError as e:
-            raise ValueError("letter %s is not in the model's alphabet" % e)
+        return _to_states(mat, code)
 
     n_walkers = int(n_ladders) * betas.size
     if isinstance(start, str):

@@ -551,6 +551,116 @@ def log_partition_tempered(hi, jij, q, n_ladders, betas, **kw):
     return res
 
 
+def annealing_schedule(n_steps, beta_min=0.1, beta_max=4.0, kind="geometric"):
+    """
+    The n_steps inverse temperatures of a schedule for `anneal`, float32, from beta_min to beta_max.
+    kind = "geometric": beta_k = beta_min (beta_max / beta_min)^(k / (K - 1)); kind = "linear": beta_k = beta_min +
+    (beta_max - beta_min) (k / (K - 1)); k = 0 .. K - 1.  Every value is computed in float64 (Python floats, the
+    operations in the order written) and rounded once to float32.  One step is beta_max alone, none is an empty array.
+    """
+    K, lo, hi_ = int(n_steps), float(beta_min), float(beta_max)
+    if K < 0 or not (0.0 < lo <= hi_ and np.isfinite(hi_)):
+        raise ValueError("need n_steps >= 0 and finite 0 < beta_min <= beta_max")
+    if kind not in ("geometric", "linear"):
+        raise ValueError('kind must be "geometric" or "linear"')
+    if K <= 1:
+        return np.array([hi_] * K, np.float32)
+    if kind == "geometric":
+        b = [lo * (hi_ / lo) ** (k / (K - 1)) for k in range(K)]
+    else:
+        b = [lo + (hi_ - lo) * (k / (K - 1)) for k in range(K)]
+    return np.array(b, np.float64).astype(np.float32)
+
+
+def anneal(hi, jij, q, n_chains, betas=None, n_steps=100, sweeps_per_step=1, max_greedy=100, seed=0, start=None, fixed=None,
+           allowed=None, first_sweep=0, steps_per_launch=0, callback=None, energies=True, device=0):
+    """
+    Simulated annealing and greedy ascent on the Potts model (hi, jij) on the GPU (plm_anneal, DESIGN_NEXT_ROWS.md section
+    9.13): the search for sequences of high statistical energy H (P(x) ~ exp H(x), higher is better).  n_chains chains make
+    sweeps_per_step Gibbs sweeps of `sample` at every inverse temperature of betas (None: annealing_schedule(n_steps); an
+    array sets n_steps, any positive finite values in any order), then at most max_greedy greedy sweeps, in which a site
+    moves to its best allowed state only when that improves H strictly.  After every step, and after the greedy sweeps,
+    a chain whose tracked gain exceeds its best so far records its states (a checkpoint).
+    start, fixed, allowed: as for `sample` (start None: the start rule at beta = 1).  first_sweep: the sweep index of the
+    first annealing sweep, to continue an earlier call from its `states`.  The steps run in launches of at most
+    steps_per_launch steps (0: about a second each; no result depends on it); callback(steps_done, n_steps) is called
+    between launches and stops the call by returning a true value (the greedy sweeps do not run then); an exception it
+    raises is raised again here.  Chain c depends on (seed, c, model, options, its start) only.
+    Returns a dict: states int8 [C, L], gain [C] (tracked H(states) - H(start)), best int8 [C, L], best_gain [C], best_at
+    int32 [C] (checkpoint 0 .. n_steps + 1), last_move int32 [C] (the last greedy sweep, from 1, in which the chain moved;
+    0: none), converged bool [C] (the chain made a greedy sweep without a move: it is a local optimum), energies and
+    best_energies float64 [C, 3] = (H, H_J, H_h) as `hamiltonians` (None with energies=False), steps_done, status
+    ("converged" or "interrupted").
+    """
+    q, C_ = int(q), int(n_chains)
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
+        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
+    L = hi.shape[0]
+    jij = np.ascontiguousarray(jij, dtype=np.float32)
+    if jij.size != L * (L - 1) // 2 * q * q:
+        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    if betas is None:
+        betas = annealing_schedule(int(n_steps))
+    betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
+    K = betas.size
+    if C_ < 1:
+        raise ValueError("need n_chains >= 1")
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.int8)
+        if start.shape != (C_, L):
+            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8)
+        if fixed.shape != (L,):
+            raise ValueError("fixed must hold L = %d flags" % L)
+    if allowed is not None:
+        allowed = np.ascontiguousarray(np.asarray(allowed).astype(bool), dtype=np.uint8)
+        if allowed.shape != (q,):
+            raise ValueError("allowed must hold q = %d flags" % q)
+    lib = _lib.load()
+    opts = _lib.PlmAnnealOpts(C_, K, int(sweeps_per_step), int(max_greedy), int(first_sweep) & 0xFFFFFFFF,
+                              int(steps_per_launch), _ptr(betas) if K else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                              _ptr(start), _ptr(fixed), _ptr(allowed))
+    out = dict(states=np.zeros((C_, L), np.int8), gain=np.zeros(C_), best=np.zeros((C_, L), np.int8),
+               best_gain=np.zeros(C_), best_at=np.zeros(C_, np.int32), last_move=np.zeros(C_, np.int32),
+               converged=np.zeros(C_, np.uint8), energies=np.zeros((C_, 3)) if energies else None,
+               best_energies=np.zeros((C_, 3)) if energies else None)
+    res = _lib.PlmAnnealResult(*[_ptr(out[k]) for k in ("states", "gain", "best", "best_gain", "best_at", "last_move",
+                                                        "converged", "energies", "best_energies")], 0, 0)
+    failure = []
+
+    def _cb(done, total, _user):
+        try:
+            return 1 if callback(int(done), int(total)) else 0
+        except BaseException as exc:     # an exception must not cross the C frames
+            failure.append(exc)
+            return 1
+
+    cb = _lib.ANNEAL_CB(_cb) if callback is not None else _lib.ANNEAL_CB()
+    check(lib.plm_anneal(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb, None, C.byref(res)))
+    if failure:
+        raise failure[0]
+    out["converged"] = out["converged"].astype(bool)
+    out["steps_done"] = int(res.steps_done)
+    out["status"] = BM_STATUS[int(res.status)]
+    return out
+
+
+def greedy_ascent(hi, jij, q, start, max_sweeps=100, fixed=None, allowed=None, device=0):
+    """
+    The local optimum of H every given sequence runs into: `anneal` without annealing steps.  start: n x L states; a
+    sweep moves every free site to its best allowed state when that improves H strictly (the first such state on equal
+    values, no move on a tie), until a sweep moves nothing or max_sweeps sweeps are made.  Returns the dict of `anneal`:
+    states are the optima where converged is set, last_move the number of sweeps that moved something.
+    """
+    start = np.ascontiguousarray(start, dtype=np.int8)
+    if start.ndim != 2:
+        raise ValueError("start must be an (n, L) matrix of states")
+    return anneal(hi, jij, q, start.shape[0], n_steps=0, max_greedy=max_sweeps, start=start, fixed=fixed, allowed=allowed,
+                  device=device)
+
+
 def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, lr_decay_after=0, lambda_h=0.0,
            lambda_j=0.0, tol=0.0, seed=0, start=None, first_epoch=0, callback=None, device=0):
     """

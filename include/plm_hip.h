@@ -483,6 +483,67 @@ typedef int (*plm_pt_cb)(int32_t rounds_done, int32_t n_rounds, void *user);
 int plm_pt(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_pt_opts *opts, int device,
            void *stream, plm_pt_cb cb, void *user, plm_pt_result *result);
 
+/* ---- simulated annealing and greedy ascent (DESIGN_NEXT_ROWS.md section 9.13) --------------------------------------
+ * Searches for sequences of high statistical energy H(x) = sum_i h_i(x_i) + sum_{i<j} J_ij(x_i, x_j) (P(x) ~ exp H(x):
+ * higher is better) of the model of plm_sample.  C independent chains; a sweep visits the sites 0 .. L-1 in that order and
+ * skips the fixed ones.  A site update computes U_a = h_i(a) + sum_{j != i} J_ij(a, x_j) in float32, from the field over
+ * j = 0 .. L-1, as plm_sample does, and is one of two kinds:
+ *   annealing at beta   the draw of plm_sample on U with that beta and the allowed mask, Philox counter (chain, 0, sweep,
+ *                       site), key (seed low, seed high): bit for bit the update of plm_sample at that beta, sweep and seed
+ *   greedy              a* = the first allowed state in state order with the largest U over the allowed states; the chain
+ *                       moves to a* iff U[a*] > U[x_i] in float32 (a tie never moves); no random numbers
+ * and after either gain += (double)U[a_new] - (double)U[a_old] in float64: the change of H up to the rounding of the two
+ * float32 sums, 0 when nothing moved.
+ * Schedule: 1. the start: opts->start, or (NULL) plm_sample's start rule at beta = 1 with the allowed mask and sweep index
+ * 0xFFFFFFFF; gain = 0; checkpoint 0: best = the start, best_gain = 0, best_at = 0.  2. step k = 1 .. K: n =
+ * sweeps_per_step annealing sweeps at betas[k-1] with the sweep indices first_sweep + (k-1) n + s, then checkpoint k: if
+ * gain > best_gain (strictly) the chain's states go to best, best_gain = gain, best_at = k.  3. at most G = max_greedy
+ * greedy sweeps, numbered from 1: a chain that completes a sweep without a move is converged and never moves again;
+ * last_move[c] is the number of the last greedy sweep in which chain c moved (0: none), converged[c] = 1 iff it completed
+ * some sweep without a move.  With G >= 1 checkpoint K + 1 follows, under the same rule.
+ * Chain c depends on (seed, c, model, options, its start) only: not on C, the launch plan, the device or how the schedule
+ * is cut into launches.  The steps run in launches of at most steps_per_launch steps (0: about a second each) and the
+ * greedy sweeps in launches of at most that many steps' sweeps; cb, if given, is called after a launch of annealing steps
+ * while work remains (further steps, or the greedy phase) and cancels by returning non-zero: status
+ * PLM_STATUS_INTERRUPTED, the greedy phase does not run, the arrays hold the state reached after steps_done steps,
+ * last_move and converged are zero.  energies / best_energies: (H, H_J, H_h) of states / best, what plm_hamiltonians
+ * returns for those rows (for n_sites == 1: (h(x), 0, h(x)), as plm_sample).
+ * PLM_EINVAL (before the device is looked at): NULL opts or result, n_sites or n_chains or sweeps_per_step below 1,
+ * n_steps, max_greedy or steps_per_launch below 0, n_steps == 0 with max_greedy == 0, betas NULL with n_steps > 0 or given
+ * with n_steps == 0, a beta that is not finite or <= 0, first_sweep + K n at or above 2^32 - 1, no allowed state;
+ * PLM_EUNSUPPORTED: q outside 2..32.  PLM_ENOMEM before any array of the model or the start is read (the expanded table,
+ * the canonical vector, 2 C L states, 28 C bytes of scalars); then PLM_EINVAL for n_chains x n_sites at or above 2^31 and
+ * for start states outside 0..q-1 or not allowed at a site that is not fixed. */
+typedef struct {
+    int32_t  n_chains;          /* C >= 1                                                               */
+    int32_t  n_steps;           /* K >= 0 annealing steps                                               */
+    int32_t  sweeps_per_step;   /* n >= 1                                                               */
+    int32_t  max_greedy;        /* G >= 0; K == 0 and G == 0 together: PLM_EINVAL                       */
+    uint32_t first_sweep;       /* sweep index of the first annealing sweep (continuation)              */
+    int32_t  steps_per_launch;  /* 0 = default; any value gives the same bits                           */
+    const float *betas;         /* K values, finite and > 0, in any order (reheating is allowed); NULL iff K == 0 */
+    uint64_t seed;
+    const int8_t  *start;       /* NULL, or C x L states                                                */
+    const uint8_t *fixed;       /* NULL, or L flags; as plm_sample: a fixed site keeps what the start gave it */
+    const uint8_t *allowed;     /* NULL, or q flags, at least one set                                   */
+} plm_anneal_opts;
+typedef struct {
+    int8_t  *states;        /* C x L final states                                                       */
+    double  *gain;          /* [C] tracked H(final) - H(start)                                          */
+    int8_t  *best;          /* C x L states at the best checkpoint                                      */
+    double  *best_gain;     /* [C]                                                                      */
+    int32_t *best_at;       /* [C] checkpoint 0 .. K + 1                                                */
+    int32_t *last_move;     /* [C]                                                                      */
+    uint8_t *converged;     /* [C]                                                                      */
+    double  *energies;      /* C x 3 (H, H_J, H_h) of `states`                                          */
+    double  *best_energies; /* C x 3 of `best`                                                          */
+    int32_t steps_done;     /* annealing steps that ran                                                 */
+    int32_t status;         /* PLM_STATUS_CONVERGED: all K steps and the greedy phase ran; else PLM_STATUS_INTERRUPTED */
+} plm_anneal_result;        /* every pointer may be NULL */
+typedef int (*plm_anneal_cb)(int32_t steps_done, int32_t n_steps, void *user);
+int plm_anneal(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_anneal_opts *opts, int device,
+               void *stream, plm_anneal_cb cb, void *user, plm_anneal_result *result);
+
 /* ---- mean-field direct coupling analysis ---------------------------
  * Replaces the arithmetic of evcouplings/couplings/mean_field.py:163-222 (MeanFieldDCA.fit: weights,
  * frequencies, pseudo-count regularisation :717-790, covariance matrix :897-940, J = -C^-1 :204-210 and
