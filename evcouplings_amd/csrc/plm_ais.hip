@@ -89,19 +89,17 @@ struct AisArgs {
 
 // the steps [k0, k1) under the plan gibbs::plan_sweeps made
 hipError_t launch_steps(const gibbs::SweepPlan &p, hipStream_t st, const AisArgs &a) {
-    const uint32_t seed_lo = (uint32_t)(a.seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(a.seed >> 32);
+    const gibbs::Seed sd(a.seed);
     return gibbs::dispatch(
         p,
         [&](auto nv, auto tile) {
-            return gibbs::launch(k_ais<nv(), tile()>, (unsigned)((a.C + tile() - 1) / tile()), tile(), p, st, a.W, a.L, a.q,
-                                 a.C, p.JC, a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed, seed_lo, seed_hi, a.states, a.e,
-                                 a.logw);
+            return gibbs::launch_tiled(k_ais<nv(), tile()>, tile(), a.C, p, st, a.W, a.L, a.q, a.C, p.JC, a.betas, a.k0, a.k1,
+                                       a.n_per, a.first, a.allowed, sd.lo, sd.hi, a.states, a.e, a.logw);
         },
         [&](auto qp) {
-            const int cpw = 256 / qp();              // chains per workgroup
-            return gibbs::launch(k_ais_direct<qp()>, (unsigned)((a.C + cpw - 1) / cpw), 256, p, st, (const float *)a.W, a.L,
-                                 a.q, p.NV * 4, a.C, a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed, seed_lo, seed_hi,
-                                 a.states, a.e, a.logw);
+            return gibbs::launch_direct(k_ais_direct<qp()>, qp(), a.C, p, st, (const float *)a.W, a.L, a.q, p.NV * 4, a.C,
+                                        a.betas, a.k0, a.k1, a.n_per, a.first, a.allowed, sd.lo, sd.hi, a.states, a.e,
+                                        a.logw);
         });
 }
 
@@ -151,23 +149,22 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
     for (int k = 0; k <= K; k++) betas[k] = opts->betas ? opts->betas[k] : (float)((double)k / (double)K);
 
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_canon = (size_t)plm_n_canon(L, q), CL = (size_t)C * L;
-    float *canon = nullptr, *d_betas = nullptr;
-    float4 *W = nullptr;
+    const size_t CL = (size_t)C * L;
+    gibbs::DeviceModel model(L, q);
+    float *d_betas = nullptr;
     int8_t *states = nullptr;
     double *d_e = nullptr, *d_logw = nullptr;
     DeviceBuffers mem;
-    PLM_TRY(mem.alloc(&canon, n_canon));
+    PLM_TRY(model.alloc_canon(mem));
     PLM_TRY(mem.alloc(&d_betas, betas.size()));
-    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(model.alloc_table(mem));
     PLM_TRY(mem.alloc(&states, CL));
     PLM_TRY(mem.alloc(&d_e, (size_t)C));
     PLM_TRY(mem.alloc(&d_logw, (size_t)C));
-    PLM_HIP(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(model.upload(st, x_canonical));
     PLM_HIP(hipMemcpyAsync(d_betas, betas.data(), betas.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    PLM_HIP(gibbs::expand(st, canon, L, q, W));
-    AisArgs args = {W, L, q, C, d_betas, 0, 0, n, 1, plm_state_mask(q), opts->seed, states, d_e,
-                    d_logw};
+    PLM_HIP(model.expand(st));
+    AisArgs args = {model.W, L, q, C, d_betas, 0, 0, n, 1, plm_state_mask(q), opts->seed, states, d_e, d_logw};
     int steps_done = 0, status = PLM_STATUS_CONVERGED;
     while (steps_done < K) {
         args.k0 = steps_done;

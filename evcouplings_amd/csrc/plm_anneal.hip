@@ -11,8 +11,9 @@
 //
 // The body is not the tempered one (plm_tempered_device.h): there U starts at zero and the temperature scales the
 // couplings only; here U starts at the field as in k_gibbs, sites can be fixed, and the greedy step draws nothing.
+// What surrounds the site loop is the frame of plm_gibbs_device.h, which all the sweep kernels share.
 #include "plm_sample_internal.h"
-#include "plm_tempered_device.h"        // pick_state
+#include "plm_gibbs_device.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -60,43 +61,20 @@ __device__ __forceinline__ int greedy_state(const float4 *U, int q, uint32_t all
 // counts as converged and writes nothing.
 template <int NV, int TILE>
 __global__ __launch_bounds__(TILE) void k_anneal(const float4 *__restrict__ W, int L, int q, int C, int JC, AnnealArgs A) {
-    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;
-    extern __shared__ float4 lds4[];
-    const int tid = threadIdx.x;
-    const int L4 = (L + 3) >> 2;
-    const int c0 = blockIdx.x * TILE;
-    const int chain = c0 + tid;
-    const int n_here = min(TILE, C - c0);
-    const int buf_f4 = JC * q * NVP;
-    float4 *stage = lds4;
-    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);
-    uint32_t *xw = (uint32_t *)xs;
-    const float4 *H = W + (int64_t)L * L * q * NV;
-    const uint32_t allowed = A.allowed;
+    GS_TILE_FRAME()
+    const uint32_t allowed = A.allowed, seed_lo = A.seed_lo, seed_hi = A.seed_hi;
 
-    for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
+    GS_ZERO_STATES()
     __syncthreads();
     if (A.start_rule) {
-        for (int i = 0; i < L; i++) {
-            float4 U[NV];
-#pragma unroll
-            for (int v = 0; v < NV; v++) U[v] = H[i * NV + v];
-            const int a = draw_state<NV>(U, q, allowed, 1.0f, philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i,
-                                                                           A.seed_lo, A.seed_hi));
-            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;
-        }
+        GS_DRAW_START(1.0f)
     } else {
-        for (int k = tid; k < n_here * L; k += TILE) {
-            const int c = k / L, j = k - c * L;
-            xs[((j >> 2) * TILE + c) * 4 + (j & 3)] = (uint8_t)A.states[(int64_t)c0 * L + k];
-        }
+        GS_LOAD_STATES(A.states)
     }
     __syncthreads();
-    if (A.start_rule)                                         // checkpoint 0
-        for (int k = tid; k < n_here * L; k += TILE) {
-            const int c = k / L, j = k - c * L;
-            A.best[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
-        }
+    if (A.start_rule) {                                       // checkpoint 0
+        GS_STORE_STATES(A.best)
+    }
     double gain = 0.0, best_gain = 0.0;
     int best_at = 0, last_move = 0;
     bool conv = true;
@@ -108,9 +86,7 @@ __global__ __launch_bounds__(TILE) void k_anneal(const float4 *__restrict__ W, i
         conv = A.converged[chain] != 0;
     }
 
-    const int n_chunks = (L + JC - 1) / JC;
-    const int row4 = q * NV;
-    uint32_t g = 0;
+    GS_TILE_PIPE()
     const int k_end = A.k1 + (A.n_greedy > 0 ? 1 : 0);       // the greedy sweeps run as one more step
     for (int k = A.k0; k < k_end; k++) {
         const bool greedy = k >= A.k1;
@@ -122,7 +98,7 @@ __global__ __launch_bounds__(TILE) void k_anneal(const float4 *__restrict__ W, i
             for (int i = 0; i < L; i++) {
                 if (A.fixed && A.fixed[i]) continue;          // uniform over the workgroup
                 GS_SITE_U(H[i * NV + v])
-                const int at = ((i >> 2) * TILE + tid) * 4 + (i & 3);
+                const int at = GS_XS(i, tid);
                 const int a_old = xs[at];
                 const float u_old = pick_state<NV>(U, a_old);
                 int a;
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(TILE) void k_anneal(const float4 *__restrict__ W, i
                     }
                 } else {
                     a = draw_state<NV>(U, q, allowed, beta,
-                                       philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, A.seed_lo, A.seed_hi));
+                                       philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
                     u_new = pick_state<NV>(U, a);
                 }
                 gain += (double)u_new - (double)u_old;
@@ -152,14 +128,11 @@ __global__ __launch_bounds__(TILE) void k_anneal(const float4 *__restrict__ W, i
         if (at_no && chain < C && gain > best_gain) {         // the checkpoint: the lane copies its own chain
             best_gain = gain;
             best_at = at_no;
-            for (int j = 0; j < L; j++) A.best[(int64_t)chain * L + j] = (int8_t)xs[((j >> 2) * TILE + tid) * 4 + (j & 3)];
+            for (int j = 0; j < L; j++) A.best[(int64_t)chain * L + j] = (int8_t)xs[GS_XS(j, tid)];
         }
     }
     __syncthreads();
-    for (int k = tid; k < n_here * L; k += TILE) {
-        const int c = k / L, j = k - c * L;
-        A.states[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
-    }
+    GS_STORE_STATES(A.states)
     if (chain < C) {
         A.gain[chain] = gain;
         A.best_gain[chain] = best_gain;
@@ -175,40 +148,21 @@ __global__ __launch_bounds__(TILE) void k_anneal(const float4 *__restrict__ W, i
 template <int QP>
 __global__ __launch_bounds__(256) void k_anneal_direct(const float *__restrict__ Wf, int L, int q, int QS, int C,
                                                        AnnealArgs A) {
-    constexpr int CPW = 256 / QP;
-    extern __shared__ float4 lds4[];
-    uint8_t *xs = (uint8_t *)lds4;
-    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;
-    const int lane0 = (tid & 63) & ~(QP - 1);                 // the group's first lane within the wave
-    const int Lp = (L + 3) & ~3;
-    const int c0 = blockIdx.x * CPW;
-    const int chain = c0 + cl;
-    const int n_here = min(CPW, C - c0);
-    const float *Hf = Wf + (int64_t)L * L * q * QS;
-    uint8_t *xc = xs + cl * Lp;
-    const uint32_t allowed = A.allowed;
+    GS_DIRECT_FRAME()
+    GS_DIRECT_XC()
+    const uint32_t allowed = A.allowed, seed_lo = A.seed_lo, seed_hi = A.seed_hi;
     const bool on = a < q && ((allowed >> a) & 1u);
-    for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
+    GS_DIRECT_ZERO()
     __syncthreads();
     if (A.start_rule) {
-        for (int i = 0; i < L; i++) {
-            const float U = a < q ? Hf[i * QS + a] : 0.f;
-            const int x = draw_group<QP>(U, a, q, allowed, 1.0f,
-                                         philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i, A.seed_lo, A.seed_hi));
-            if (a == 0) xc[i] = (uint8_t)x;
-        }
+        GS_DIRECT_DRAW_START(1.0f)
     } else {
-        for (int k = tid; k < n_here * L; k += 256) {
-            const int c = k / L, j = k - c * L;
-            xs[c * Lp + j] = (uint8_t)A.states[(int64_t)c0 * L + k];
-        }
+        GS_DIRECT_LOAD(A.states)
     }
     __syncthreads();
-    if (A.start_rule)                                         // checkpoint 0
-        for (int k = tid; k < n_here * L; k += 256) {
-            const int c = k / L, j = k - c * L;
-            A.best[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
-        }
+    if (A.start_rule) {                                       // checkpoint 0
+        GS_DIRECT_STORE(A.best)
+    }
     double gain = 0.0, best_gain = 0.0;
     int best_at = 0, last_move = 0;
     bool conv = true;
@@ -229,13 +183,7 @@ __global__ __launch_bounds__(256) void k_anneal_direct(const float *__restrict__
             bool moved = false;
             for (int i = 0; i < L; i++) {
                 if (A.fixed && A.fixed[i]) continue;
-                const float *Wi = Wf + (int64_t)i * L * q * QS;
-                float U = a < q ? Hf[i * QS + a] : 0.f;
-                for (int j = 0; j < L; j++) {
-                    if (j == i) continue;
-                    const int x = xc[j];
-                    if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-                }
+                GS_DIRECT_SITE_U(a < q ? Hf[i * QS + a] : 0.f)
                 const int x_old = xc[i];
                 const float u_old = __shfl(U, lane0 + x_old, 64);
                 int x;
@@ -256,7 +204,7 @@ __global__ __launch_bounds__(256) void k_anneal_direct(const float *__restrict__
                     u_new = go ? m : u_old;
                 } else {
                     x = draw_group<QP>(U, a, q, allowed, beta,
-                                       philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, A.seed_lo, A.seed_hi));
+                                       philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
                     u_new = __shfl(U, lane0 + x, 64);
                 }
                 gain += (double)u_new - (double)u_old;
@@ -278,10 +226,7 @@ __global__ __launch_bounds__(256) void k_anneal_direct(const float *__restrict__
         }
     }
     __syncthreads();
-    for (int k = tid; k < n_here * L; k += 256) {
-        const int c = k / L, j = k - c * L;
-        A.states[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
-    }
+    GS_DIRECT_STORE(A.states)
     if (a == 0 && chain < C) {
         A.gain[chain] = gain;
         A.best_gain[chain] = best_gain;
@@ -297,13 +242,10 @@ hipError_t launch_anneal(const gibbs::SweepPlan &p, hipStream_t st, const float4
     return gibbs::dispatch(
         p,
         [&](auto nv, auto tile) {
-            return gibbs::launch(k_anneal<nv(), tile()>, (unsigned)((C + tile() - 1) / tile()), tile(), p, st, W, L, q, C,
-                                 p.JC, a);
+            return gibbs::launch_tiled(k_anneal<nv(), tile()>, tile(), C, p, st, W, L, q, C, p.JC, a);
         },
         [&](auto qp) {
-            const int cpw = 256 / qp();              // chains per workgroup
-            return gibbs::launch(k_anneal_direct<qp()>, (unsigned)((C + cpw - 1) / cpw), 256, p, st, (const float *)W, L, q,
-                                 p.NV * 4, C, a);
+            return gibbs::launch_direct(k_anneal_direct<qp()>, qp(), C, p, st, (const float *)W, L, q, p.NV * 4, C, a);
         });
 }
 
@@ -326,14 +268,8 @@ int plm_anneal(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
             return plm_fail(PLM_EINVAL, "betas must be finite and > 0 (betas[%d] = %g)", k, (double)opts->betas[k]);
     if ((double)opts->first_sweep + (double)K * (double)n >= 4294967295.0)
         return plm_fail(PLM_EINVAL, "first_sweep + n_steps x sweeps_per_step must stay below 2^32 - 1 sweeps");
-    uint32_t allowed = plm_state_mask(q);
-    if (opts->allowed) {
-        uint32_t m = 0;
-        for (int a = 0; a < q; a++)
-            if (opts->allowed[a]) m |= 1u << a;
-        if (!m) return plm_fail(PLM_EINVAL, "no state is allowed");
-        allowed = m;
-    }
+    uint32_t allowed = 0;
+    PLM_TRY(gibbs::allowed_mask(q, opts->allowed, &allowed));
     PLM_TRY(plm_check_device(device));
     // sizes first: nothing below this point is dereferenced before the device is known to hold the call
     const double table_b = gibbs::table_bytes(L, q);
@@ -356,14 +292,14 @@ int plm_anneal(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
                                      : gibbs::default_steps_per_launch(plan, L, C, 1, G, n_cu);
 
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_canon = (size_t)plm_n_canon(L, q), CL = (size_t)C * L;
-    float *canon = nullptr, *d_betas = nullptr;
-    float4 *W = nullptr;
+    const size_t CL = (size_t)C * L;
+    gibbs::DeviceModel model(L, q);
+    float *d_betas = nullptr;
     AnnealArgs a = {};
     uint8_t *fixed = nullptr;
     DeviceBuffers mem;
-    PLM_TRY(mem.alloc(&canon, n_canon));
-    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(model.alloc_canon(mem));
+    PLM_TRY(model.alloc_table(mem));
     PLM_TRY(mem.alloc(&a.states, CL));
     PLM_TRY(mem.alloc(&a.best, CL));
     PLM_TRY(mem.alloc(&a.gain, (size_t)C));
@@ -373,7 +309,7 @@ int plm_anneal(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
     PLM_TRY(mem.alloc(&a.converged, (size_t)C));
     if (K > 0) PLM_TRY(mem.alloc(&d_betas, (size_t)K));
     if (opts->fixed) PLM_TRY(mem.alloc(&fixed, (size_t)L));
-    PLM_HIP(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(model.upload(st, x_canonical));
     if (K > 0) PLM_HIP(hipMemcpyAsync(d_betas, opts->betas, (size_t)K * sizeof(float), hipMemcpyHostToDevice, st));
     if (fixed) PLM_HIP(hipMemcpyAsync(fixed, opts->fixed, (size_t)L, hipMemcpyHostToDevice, st));
     if (opts->start) {                                        // checkpoint 0 of given states
@@ -385,21 +321,22 @@ int plm_anneal(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
     PLM_HIP(hipMemsetAsync(a.best_at, 0, (size_t)C * sizeof(int32_t), st));
     PLM_HIP(hipMemsetAsync(a.last_move, 0, (size_t)C * sizeof(int32_t), st));
     PLM_HIP(hipMemsetAsync(a.converged, 0, (size_t)C, st));
-    PLM_HIP(gibbs::expand(st, canon, L, q, W));
+    PLM_HIP(model.expand(st));
     a.betas = d_betas;
     a.fixed = fixed;
     a.n_per = n;
     a.start_rule = opts->start ? 0 : 1;
     a.first_sweep = opts->first_sweep;
     a.allowed = allowed;
-    a.seed_lo = (uint32_t)(opts->seed & 0xFFFFFFFFu);
-    a.seed_hi = (uint32_t)(opts->seed >> 32);
+    const gibbs::Seed seed(opts->seed);
+    a.seed_lo = seed.lo;
+    a.seed_hi = seed.hi;
 
     int steps_done = 0, status = PLM_STATUS_CONVERGED;
     while (steps_done < K) {
         a.k0 = steps_done;
         a.k1 = std::min(K, steps_done + per_launch);
-        PLM_HIP(launch_anneal(plan, st, W, L, q, C, a));
+        PLM_HIP(launch_anneal(plan, st, model.W, L, q, C, a));
         a.start_rule = 0;
         steps_done = a.k1;
         if (cb && (steps_done < K || G > 0)) {
@@ -416,7 +353,7 @@ int plm_anneal(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
             a.n_greedy = std::min(greedy_per_launch, G - done);
             a.greedy_done = done;
             a.final_at = done + a.n_greedy == G ? K + 1 : 0;
-            PLM_HIP(launch_anneal(plan, st, W, L, q, C, a));
+            PLM_HIP(launch_anneal(plan, st, model.W, L, q, C, a));
             a.start_rule = 0;
         }
     }

@@ -1,7 +1,7 @@
 // plm_gibbs_device.h -- the device code every sweep kernel shares: the Philox block, the uniform, the draw of the
-// contract in its two forms, and the staging pipeline of the tiled form (DESIGN_NEXT_ROWS.md section 9.6).  Included by
-// plm_sample.hip (k_gibbs*) and, through plm_tempered_device.h, by plm_ais.hip and plm_pt.hip; everything here has
-// internal linkage.
+// contract in its two forms, the staging pipeline of the tiled form (DESIGN_NEXT_ROWS.md section 9.6) and the frame of
+// either form around the site loop (section 9.14).  Included by plm_sample.hip (k_gibbs*), plm_anneal.hip (k_anneal*)
+// and, through plm_tempered_device.h, by plm_ais.hip and plm_pt.hip; everything here has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -151,6 +151,115 @@ _Pragma("unroll") \
         GS_STEP(base, pre0);                                                            \
         GS_STEP(base + 1, pre1);                                                        \
         GS_STEP(base + 2, pre2);                                                        \
+    }
+
+// U_a of a state known only at run time, as a chain of selects over the NV 4 registers (an indexed array would live in
+// scratch memory)
+template <int NV>
+__device__ __forceinline__ float pick_state(const float4 *U, int a) {
+    float r = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        r = a == 4 * v + 0 ? U[v].x : r;
+        r = a == 4 * v + 1 ? U[v].y : r;
+        r = a == 4 * v + 2 ? U[v].z : r;
+        r = a == 4 * v + 3 ? U[v].w : r;
+    }
+    return r;
+}
+
+// The frame of the tiled form, once for k_gibbs, tempered_tile and k_anneal: everything around their site loops, as
+// text over the kernel's names (NV, TILE, W, L, q, C, JC, and allowed, seed_lo, seed_hi for the start rule).  The site
+// loops and the order in which a kernel opens are its own (sections 9.10, 9.13, 9.14).
+// GS_TILE_FRAME and GS_TILE_PIPE declare the locals GS_SITE_U / GS_STEP use by name, in two parts because the place of
+// the second changes the code: the tempered body declares it at the top, k_gibbs and k_anneal before their sweeps.
+// The chain states of the tile live in LDS behind the two staging buffers as xs[L/4][TILE][4] bytes: a lane reads four
+// consecutive sites of its chain with one ds_read_b32, the 64 lanes of a wave 256 consecutive bytes.
+#define GS_TILE_FRAME()                                                                                        \
+    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;                                                           \
+    extern __shared__ float4 lds4[];                                                                           \
+    const int tid = threadIdx.x;                                                                               \
+    const int L4 = (L + 3) >> 2;                                                                               \
+    const int c0 = blockIdx.x * TILE;                                                                          \
+    const int chain = c0 + tid;                                                                                \
+    const int n_here = min(TILE, C - c0);                                                                      \
+    const int buf_f4 = JC * q * NVP;                         /* one staging buffer, in float4 */               \
+    float4 *stage = lds4;                                                                                      \
+    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);                                                              \
+    uint32_t *xw = (uint32_t *)xs;                                                                             \
+    const float4 *H = W + (int64_t)L * L * q * NV;
+#define GS_TILE_PIPE()                                                                                         \
+    const int n_chunks = (L + JC - 1) / JC;                                                                    \
+    const int row4 = q * NV;                                 /* float4 of one block W[i][j] */                 \
+    uint32_t g = 0;                                          /* chunks staged so far: the LDS buffer alternates with it */
+// the byte of site i of the tile's chain `lane` in xs
+#define GS_XS(i, lane) ((((i) >> 2) * TILE + (lane)) * 4 + ((i) & 3))
+#define GS_ZERO_STATES() for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
+// the start rule: one draw per site of softmax beta h_i
+#define GS_DRAW_START(beta_)                                                                                   \
+    for (int i = 0; i < L; i++) {                                                                              \
+        float4 Hi[NV];                                                                                         \
+        _Pragma("unroll") for (int v = 0; v < NV; v++) Hi[v] = H[i * NV + v];                                  \
+        const int a = draw_state<NV>(Hi, q, allowed, (beta_), philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, \
+                                                                           (uint32_t)i, seed_lo, seed_hi));    \
+        xs[GS_XS(i, tid)] = (uint8_t)a;                                                                        \
+    }
+// the states of the tile's chains from and to global memory, [C][L]
+#define GS_LOAD_STATES(src_)                                                                                   \
+    for (int k = tid; k < n_here * L; k += TILE) {                                                             \
+        const int c = k / L, j = k - c * L;                                                                    \
+        xs[GS_XS(j, c)] = (uint8_t)(src_)[(int64_t)c0 * L + k];                                                \
+    }
+#define GS_STORE_STATES(dst_)                                                                                  \
+    for (int k = tid; k < n_here * L; k += TILE) {                                                             \
+        const int c = k / L, j = k - c * L;                                                                    \
+        (dst_)[(int64_t)c0 * L + k] = (int8_t)xs[GS_XS(j, c)];                                                 \
+    }
+
+// The frame of the direct form, once for k_gibbs_direct, tempered_direct and k_anneal_direct, over the kernel's names
+// (QP, Wf, L, q, QS, C, and allowed, seed_lo, seed_hi for the start rule): lanes = (chain, state), 256 / QP chains per
+// workgroup, the chain states in LDS as xs[chain][Lp] bytes.  xc, the states of the lane's chain, is GS_DIRECT_XC() at
+// the place each kernel declared it: the place changes the code the compiler makes (section 9.14).
+#define GS_DIRECT_FRAME()                                                                                      \
+    constexpr int CPW = 256 / QP;                                                                              \
+    extern __shared__ float4 lds4[];                                                                           \
+    uint8_t *xs = (uint8_t *)lds4;                                                                             \
+    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;                                                  \
+    const int lane0 = (tid & 63) & ~(QP - 1);                /* the group's first lane within the wave */      \
+    (void)lane0;                                                                                               \
+    const int Lp = (L + 3) & ~3;                                                                               \
+    const int c0 = blockIdx.x * CPW;                                                                           \
+    const int chain = c0 + cl;                                                                                 \
+    const int n_here = min(CPW, C - c0);                                                                       \
+    const float *Hf = Wf + (int64_t)L * L * q * QS;
+#define GS_DIRECT_XC() uint8_t *xc = xs + cl * Lp;
+// U_a = init + sum_{j != i} J_ij(a, x_j) of the group's chain in float32, j = 0 .. L-1, for site i; init (the field or
+// zero) is read after Wi.  Declares Wi and U, as GS_SITE_U does.
+#define GS_DIRECT_SITE_U(init)                                                                                 \
+    const float *Wi = Wf + (int64_t)i * L * q * QS;                                                            \
+    float U = (init);                                                                                          \
+    for (int j = 0; j < L; j++) {                                                                              \
+        if (j == i) continue;                                                                                  \
+        const int x = xc[j];                                                                                   \
+        if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];                                                     \
+    }
+#define GS_DIRECT_ZERO() for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
+#define GS_DIRECT_DRAW_START(beta_)                                                                            \
+    for (int i = 0; i < L; i++) {                                                                              \
+        const float Hi = a < q ? Hf[i * QS + a] : 0.f;                                                         \
+        const int x = draw_group<QP>(Hi, a, q, allowed, (beta_), philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, \
+                                                                              (uint32_t)i, seed_lo, seed_hi)); \
+        if (a == 0) xs[cl * Lp + i] = (uint8_t)x;                                                              \
+    }
+#define GS_DIRECT_LOAD(src_)                                                                                   \
+    for (int k = tid; k < n_here * L; k += 256) {                                                              \
+        const int c = k / L, j = k - c * L;                                                                    \
+        xs[c * Lp + j] = (uint8_t)(src_)[(int64_t)c0 * L + k];                                                 \
+    }
+#define GS_DIRECT_STORE(dst_)                                                                                  \
+    for (int k = tid; k < n_here * L; k += 256) {                                                              \
+        const int c = k / L, j = k - c * L;                                                                    \
+        (dst_)[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];                                                  \
     }
 
 // The same draw with one lane per state (groups of QP lanes, QP a power of two >= q): the maximum by a butterfly, the

@@ -130,26 +130,24 @@ struct PtArgs {
     uint32_t sweep0;
     int n_sweeps, mode;
     uint32_t allowed;
-    uint64_t seed;
+    gibbs::Seed seed;
     int8_t *states;
     double *e;
 };
 
 // n_sweeps sweeps of every walker under the plan gibbs::plan_sweeps made
 hipError_t launch_sweeps(const gibbs::SweepPlan &p, hipStream_t st, const PtArgs &a) {
-    const uint32_t seed_lo = (uint32_t)(a.seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(a.seed >> 32);
     return gibbs::dispatch(
         p,
         [&](auto nv, auto tile) {
-            return gibbs::launch(k_pt<nv(), tile()>, (unsigned)((a.C + tile() - 1) / tile()), tile(), p, st, a.W, a.L, a.q,
-                                 a.C, p.JC, a.ladder, a.rung_of_slot, a.sweep0, a.n_sweeps, a.mode, a.allowed, seed_lo,
-                                 seed_hi, a.states, a.e);
+            return gibbs::launch_tiled(k_pt<nv(), tile()>, tile(), a.C, p, st, a.W, a.L, a.q, a.C, p.JC, a.ladder,
+                                       a.rung_of_slot, a.sweep0, a.n_sweeps, a.mode, a.allowed, a.seed.lo, a.seed.hi,
+                                       a.states, a.e);
         },
         [&](auto qp) {
-            const int cpw = 256 / qp();              // walkers per workgroup
-            return gibbs::launch(k_pt_direct<qp()>, (unsigned)((a.C + cpw - 1) / cpw), 256, p, st, (const float *)a.W, a.L,
-                                 a.q, p.NV * 4, a.C, a.ladder, a.rung_of_slot, a.sweep0, a.n_sweeps, a.mode, a.allowed,
-                                 seed_lo, seed_hi, a.states, a.e);
+            return gibbs::launch_direct(k_pt_direct<qp()>, qp(), a.C, p, st, (const float *)a.W, a.L, a.q, p.NV * 4, a.C,
+                                        a.ladder, a.rung_of_slot, a.sweep0, a.n_sweeps, a.mode, a.allowed, a.seed.lo,
+                                        a.seed.hi, a.states, a.e);
         });
 }
 
@@ -208,17 +206,17 @@ int plm_pt(int32_t n_sites, int32_t n_states, const float *x_canonical, const pl
     PLM_TRY(gibbs::plan_sweeps(L, q, CR, device, &plan));
 
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_canon = (size_t)plm_n_canon(L, q), WL = (size_t)CR * L, snap_rows = (size_t)C * RO;
-    float *canon = nullptr, *d_ladder = nullptr;
-    float4 *W = nullptr;
+    const size_t WL = (size_t)CR * L, snap_rows = (size_t)C * RO;
+    gibbs::DeviceModel model(L, q);
+    float *d_ladder = nullptr;
     int8_t *states = nullptr, *snap_x = nullptr;
     double *d_e = nullptr, *snap_e = nullptr;
     int *d_ros = nullptr, *d_sor = nullptr;
     unsigned long long *d_acc = nullptr;
     DeviceBuffers mem;
-    PLM_TRY(mem.alloc(&canon, n_canon));
+    PLM_TRY(model.alloc_canon(mem));
     PLM_TRY(mem.alloc(&d_ladder, (size_t)R));
-    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(model.alloc_table(mem));
     PLM_TRY(mem.alloc(&states, WL));
     PLM_TRY(mem.alloc(&d_e, (size_t)CR));
     PLM_TRY(mem.alloc(&d_ros, (size_t)CR));
@@ -226,7 +224,7 @@ int plm_pt(int32_t n_sites, int32_t n_states, const float *x_canonical, const pl
     PLM_TRY(mem.alloc(&d_acc, (size_t)R));
     PLM_TRY(mem.alloc(&snap_x, (size_t)K * snap_rows * L));
     PLM_TRY(mem.alloc(&snap_e, (size_t)K * snap_rows));
-    PLM_HIP(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(model.upload(st, x_canonical));
     PLM_HIP(hipMemcpyAsync(d_ladder, opts->betas, (size_t)R * sizeof(float), hipMemcpyHostToDevice, st));
     PLM_HIP(hipMemcpyAsync(d_ros, ros.data(), (size_t)CR * sizeof(int), hipMemcpyHostToDevice, st));
     PLM_HIP(hipMemcpyAsync(d_sor, sor.data(), (size_t)CR * sizeof(int), hipMemcpyHostToDevice, st));
@@ -235,10 +233,10 @@ int plm_pt(int32_t n_sites, int32_t n_states, const float *x_canonical, const pl
     PLM_HIP(hipMemsetAsync(snap_e, 0, (size_t)K * snap_rows * sizeof(double), st));
     if (opts->start) PLM_HIP(hipMemcpyAsync(states, opts->start, WL, hipMemcpyHostToDevice, st));
     if (opts->start_e) PLM_HIP(hipMemcpyAsync(d_e, opts->start_e, (size_t)CR * sizeof(double), hipMemcpyHostToDevice, st));
-    PLM_HIP(gibbs::expand(st, canon, L, q, W));
+    PLM_HIP(model.expand(st));
 
-    const uint32_t seed_lo = (uint32_t)(opts->seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(opts->seed >> 32);
-    PtArgs args = {W, L, q, CR, d_ladder, d_ros, 0u, 0, opts->start ? PT_MEASURE : PT_START_RULE, allowed, opts->seed,
+    const gibbs::Seed seed(opts->seed);
+    PtArgs args = {model.W, L, q, CR, d_ladder, d_ros, 0u, 0, opts->start ? PT_MEASURE : PT_START_RULE, allowed, seed,
                    states, d_e};
     if (!opts->start_e) PLM_HIP(launch_sweeps(plan, st, args));      // the walkers' start: no sweeps
     args.mode = PT_CONTINUE;
@@ -261,7 +259,7 @@ int plm_pt(int32_t n_sites, int32_t n_states, const float *x_canonical, const pl
         if (n_pairs > 0) {
             const dim3 grid((unsigned)((C + 255) / 256), (unsigned)std::min(n_pairs, 65535));
             hipLaunchKernelGGL(k_pt_swap, grid, dim3(256), 0, st, C, R, parity, n_pairs, g, d_ladder, d_e, d_ros, d_sor,
-                               seed_lo, seed_hi, d_acc);
+                               seed.lo, seed.hi, d_acc);
             PLM_HIP(hipGetLastError());
         }
         done++;

@@ -55,8 +55,8 @@ __global__ __launch_bounds__(256) void k_sample_expand(const float *__restrict__
     W[t] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-// Chain states of the tile live in LDS as xs[L/4][TILE][4] bytes: a lane reads four consecutive sites of its chain with
-// one ds_read_b32, and the 64 lanes of a wave read 256 consecutive bytes.  A chunk of JC blocks W[i][j0 .. j0+JC) is
+// The frame (locals, the chain states in LDS, start rule, loads and stores) is GS_TILE_FRAME and its companions in
+// plm_gibbs_device.h, shared with the tempered and the annealing kernels.  A chunk of JC blocks W[i][j0 .. j0+JC) is
 // contiguous in global memory; the workgroup copies it into one of two LDS buffers (rows padded from NV to NVP float4
 // so that 16 lanes with 16 different rows hit 16 different 4-bank groups of a ds_read_b128) while it computes from the
 // other.  Sites are visited 0 .. L-1, and U accumulates in float32 over j = 0 .. L-1 without i: the order of the
@@ -67,42 +67,19 @@ __global__ __launch_bounds__(TILE) void k_gibbs(const float4 *__restrict__ W, in
                                                 const uint8_t *__restrict__ fixed /* [L] or NULL */, uint32_t allowed,
                                                 float beta, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep0,
                                                 int n_sweeps, int8_t *__restrict__ dst /* [C][L] */) {
-    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;
-    extern __shared__ float4 lds4[];
-    const int tid = threadIdx.x;
-    const int L4 = (L + 3) >> 2;
-    const int c0 = blockIdx.x * TILE;
-    const int chain = c0 + tid;
-    const int n_here = min(TILE, C - c0);
-    const int buf_f4 = JC * q * NVP;                          // one staging buffer, in float4
-    float4 *stage = lds4;
-    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);
-    uint32_t *xw = (uint32_t *)xs;
-    const float4 *H = W + (int64_t)L * L * q * NV;
+    GS_TILE_FRAME()
 
     // ---- initial states ----
-    for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
+    GS_ZERO_STATES()
     __syncthreads();
     if (src) {
-        for (int k = tid; k < n_here * L; k += TILE) {
-            const int c = k / L, j = k - c * L;
-            xs[((j >> 2) * TILE + c) * 4 + (j & 3)] = (uint8_t)src[(int64_t)c0 * L + k];
-        }
+        GS_LOAD_STATES(src)
     } else {
-        for (int i = 0; i < L; i++) {
-            float4 U[NV];
-#pragma unroll
-            for (int v = 0; v < NV; v++) U[v] = H[i * NV + v];
-            const int a = draw_state<NV>(U, q, allowed, beta, philox_word0((uint32_t)chain, 0u, GS_START_SWEEP,
-                                                                           (uint32_t)i, seed_lo, seed_hi));
-            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;
-        }
+        GS_DRAW_START(beta)
     }
     __syncthreads();
 
-    const int n_chunks = (L + JC - 1) / JC;
-    const int row4 = q * NV;                                  // float4 of one block W[i][j]
-    uint32_t g = 0;                                           // chunks staged so far: the LDS buffer alternates with it
+    GS_TILE_PIPE()
     for (int s = 0; s < n_sweeps; s++) {
         const uint32_t sweep = sweep0 + (uint32_t)s;
         for (int i = 0; i < L; i++) {
@@ -110,14 +87,11 @@ __global__ __launch_bounds__(TILE) void k_gibbs(const float4 *__restrict__ W, in
             GS_SITE_U(H[i * NV + v])
             const int a = draw_state<NV>(U, q, allowed, beta,
                                          philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
-            xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;   // a lane reads only its own chain: no barrier
+            xs[GS_XS(i, tid)] = (uint8_t)a;                   // a lane reads only its own chain: no barrier
         }
     }
     __syncthreads();
-    for (int k = tid; k < n_here * L; k += TILE) {
-        const int c = k / L, j = k - c * L;
-        dst[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
-    }
+    GS_STORE_STATES(dst)
 }
 
 // The other form of the sweep: lanes = (chain, state), 256 / QP chains per workgroup, the row W[i][j][x_cj][.] read
@@ -130,54 +104,29 @@ __global__ __launch_bounds__(256) void k_gibbs_direct(const float *__restrict__ 
                                                       const int8_t *__restrict__ src, const uint8_t *__restrict__ fixed,
                                                       uint32_t allowed, float beta, uint32_t seed_lo, uint32_t seed_hi,
                                                       uint32_t sweep0, int n_sweeps, int8_t *__restrict__ dst) {
-    constexpr int CPW = 256 / QP;
-    extern __shared__ float4 lds4[];
-    uint8_t *xs = (uint8_t *)lds4;
-    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;
-    const int Lp = (L + 3) & ~3;
-    const int c0 = blockIdx.x * CPW;
-    const int chain = c0 + cl;
-    const int n_here = min(CPW, C - c0);
-    const float *Hf = Wf + (int64_t)L * L * q * QS;
-    for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
+    GS_DIRECT_FRAME()
+    GS_DIRECT_ZERO()
     __syncthreads();
     if (src) {
-        for (int k = tid; k < n_here * L; k += 256) {
-            const int c = k / L, j = k - c * L;
-            xs[c * Lp + j] = (uint8_t)src[(int64_t)c0 * L + k];
-        }
+        GS_DIRECT_LOAD(src)
     } else {
-        for (int i = 0; i < L; i++) {
-            const float U = a < q ? Hf[i * QS + a] : 0.f;
-            const int x = draw_group<QP>(U, a, q, allowed, beta,
-                                         philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i, seed_lo, seed_hi));
-            if (a == 0) xs[cl * Lp + i] = (uint8_t)x;
-        }
+        GS_DIRECT_DRAW_START(beta)
     }
     __syncthreads();
     for (int s = 0; s < n_sweeps; s++) {
         const uint32_t sweep = sweep0 + (uint32_t)s;
         for (int i = 0; i < L; i++) {
             if (fixed && fixed[i]) continue;
-            const float *Wi = Wf + (int64_t)i * L * q * QS;
-            float U = a < q ? Hf[i * QS + a] : 0.f;
-            const uint8_t *xc = xs + cl * Lp;
-            for (int j = 0; j < L; j++) {
-                if (j == i) continue;
-                const int x = xc[j];
-                if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-            }
+            GS_DIRECT_XC()
+            GS_DIRECT_SITE_U(a < q ? Hf[i * QS + a] : 0.f)
             const int x = draw_group<QP>(U, a, q, allowed, beta,
                                          philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
-            if (a == 0) xs[cl * Lp + i] = (uint8_t)x;
+            if (a == 0) xc[i] = (uint8_t)x;
             __syncthreads();
         }
     }
     __syncthreads();
-    for (int k = tid; k < n_here * L; k += 256) {
-        const int c = k / L, j = k - c * L;
-        dst[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
-    }
+    GS_DIRECT_STORE(dst)
 }
 
 // (H, H_J, H_h) = (h(x), 0, h(x)) of the one-site model
@@ -318,6 +267,15 @@ int check_start(const int8_t *start, int C, int L, int q, uint32_t allowed, cons
     return PLM_OK;
 }
 
+int allowed_mask(int q, const uint8_t *flags, uint32_t *out) {
+    uint32_t m = flags ? 0u : plm_state_mask(q);
+    for (int a = 0; flags && a < q; a++)
+        if (flags[a]) m |= 1u << a;
+    if (!m) return plm_fail(PLM_EINVAL, "no state is allowed");
+    *out = m;
+    return PLM_OK;
+}
+
 int plan_sweeps(int L, int q, int C, int device, SweepPlan *out) {
     hipDeviceProp_t prop;
     PLM_HIP(hipGetDeviceProperties(&prop, device));
@@ -335,17 +293,16 @@ hipError_t expand(hipStream_t st, const float *canon, int L, int q, float4 *W) {
 hipError_t sweeps(const SweepPlan &p, hipStream_t st, const float4 *W, int L, int q, int C, const int8_t *src,
                   const uint8_t *fixed, uint32_t allowed, float beta, uint64_t seed, uint32_t sweep0, int n_sweeps,
                   int8_t *dst) {
-    const uint32_t seed_lo = (uint32_t)(seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(seed >> 32);
+    const Seed sd(seed);
     return dispatch(
         p,
         [&](auto nv, auto tile) {
-            return launch(k_gibbs<nv(), tile()>, (unsigned)((C + tile() - 1) / tile()), tile(), p, st, W, L, q, C, p.JC, src,
-                          fixed, allowed, beta, seed_lo, seed_hi, sweep0, n_sweeps, dst);
+            return launch_tiled(k_gibbs<nv(), tile()>, tile(), C, p, st, W, L, q, C, p.JC, src, fixed, allowed, beta, sd.lo,
+                                sd.hi, sweep0, n_sweeps, dst);
         },
         [&](auto qp) {
-            const int cpw = 256 / qp();              // chains per workgroup
-            return launch(k_gibbs_direct<qp()>, (unsigned)((C + cpw - 1) / cpw), 256, p, st, (const float *)W, L, q,
-                          p.NV * 4, C, src, fixed, allowed, beta, seed_lo, seed_hi, sweep0, n_sweeps, dst);
+            return launch_direct(k_gibbs_direct<qp()>, qp(), C, p, st, (const float *)W, L, q, p.NV * 4, C, src, fixed,
+                                 allowed, beta, sd.lo, sd.hi, sweep0, n_sweeps, dst);
         });
 }
 
@@ -437,45 +394,38 @@ int plm_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, cons
     PLM_TRY(plm_check_free(table_b + gibbs::canon_bytes(L, q) + state_b + energy_b, "the sampler", table_b));
     PLM_TRY(gibbs::check_chain_sites(C, L));
     if (!x_canonical || !samples_out) return plm_fail(PLM_EINVAL, "NULL argument");
-    uint32_t allowed = plm_state_mask(q);
-    if (opts->allowed) {
-        uint32_t m = 0;
-        for (int a = 0; a < q; a++)
-            if (opts->allowed[a]) m |= 1u << a;
-        if (!m) return plm_fail(PLM_EINVAL, "no state is allowed");
-        allowed = m;
-    }
+    uint32_t allowed = 0;
+    PLM_TRY(gibbs::allowed_mask(q, opts->allowed, &allowed));
     if (opts->start) PLM_TRY(gibbs::check_start(opts->start, C, L, q, allowed, opts->fixed));
     Plan plan;
     PLM_TRY(gibbs::plan_sweeps(L, q, C, device, &plan));
     hipStream_t st = (hipStream_t)stream;
-    const size_t n_canon = (size_t)plm_n_canon(L, q), CL = (size_t)C * L;
-    float *canon = nullptr;
-    float4 *W = nullptr;
+    const size_t CL = (size_t)C * L;
+    gibbs::DeviceModel model(L, q);
     int8_t *start = nullptr, *snaps = nullptr;
     uint8_t *fixed = nullptr;
     double *en = nullptr;
     DeviceBuffers mem;
-    PLM_TRY(mem.alloc(&canon, n_canon));
-    PLM_TRY(mem.alloc(&W, gibbs::table_float4(L, q)));
+    PLM_TRY(model.alloc_canon(mem));
+    PLM_TRY(model.alloc_table(mem));
     PLM_TRY(mem.alloc(&snaps, CL * (size_t)K));
     if (opts->start) PLM_TRY(mem.alloc(&start, CL));
     if (opts->fixed) PLM_TRY(mem.alloc(&fixed, (size_t)L));
     if (energies_out && L == 1) PLM_TRY(mem.alloc(&en, CL * (size_t)K * 3));
-    PLM_HIP(hipMemcpyAsync(canon, x_canonical, n_canon * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(model.upload(st, x_canonical));
     if (start) PLM_HIP(hipMemcpyAsync(start, opts->start, CL, hipMemcpyHostToDevice, st));
     if (fixed) PLM_HIP(hipMemcpyAsync(fixed, opts->fixed, (size_t)L, hipMemcpyHostToDevice, st));
-    PLM_HIP(gibbs::expand(st, canon, L, q, W));
+    PLM_HIP(model.expand(st));
     for (int k = 0; k < K; k++) {
         const int8_t *src = k == 0 ? start : snaps + (size_t)(k - 1) * CL;
         const uint32_t sweep0 = k == 0 ? 0u : (uint32_t)opts->burn_in + (uint32_t)(k - 1) * (uint32_t)thin;
-        PLM_HIP(gibbs::sweeps(plan, st, W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0,
+        PLM_HIP(gibbs::sweeps(plan, st, model.W, L, q, C, src, fixed, allowed, opts->beta, opts->seed, sweep0,
                               k == 0 ? opts->burn_in : thin, snaps + (size_t)k * CL));
     }
     PLM_HIP(hipMemcpyAsync(samples_out, snaps, CL * (size_t)K, hipMemcpyDeviceToHost, st));
     if (en) {
         const int64_t n = (int64_t)CL * K;
-        hipLaunchKernelGGL(k_field_energy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, canon, snaps, n, en);
+        hipLaunchKernelGGL(k_field_energy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, model.canon, snaps, n, en);
         PLM_HIP(hipGetLastError());
         PLM_HIP(hipMemcpyAsync(energies_out, en, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     }

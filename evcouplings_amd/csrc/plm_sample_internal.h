@@ -1,7 +1,8 @@
 // plm_sample_internal.h -- what plm_sample.hip shares with plm_ais.hip, plm_pt.hip, plm_anneal.hip and plm_bm.hip: the
-// checks the five entry points (plm_sample, plm_ais, plm_pt, plm_anneal, plm_bm_fit) open with, the plan, the expansion of
-// the couplings, the sweep launchers, the energies of the states returned, and the step from a plan to the template
-// arguments of a sweep kernel.
+// checks the five entry points (plm_sample, plm_ais, plm_pt, plm_anneal, plm_bm_fit) open with, the mask of the allowed
+// states, the two words of a seed, the plan, the model on the device and the expansion of its couplings, the sweep
+// launchers, the energies of the states returned, and the step from a plan to the template arguments and the grid of a
+// sweep kernel.
 #pragma once
 #include "plm_host_util.h"
 #include <type_traits>
@@ -21,6 +22,14 @@ double table_bytes(int L, int q);                     // the expanded table
 double canon_bytes(int L, int q);                     // one float32 vector in the canonical layout
 // start [C][L]: every state in 0 .. q-1 and, unless its site is fixed (fixed may be NULL), allowed; or PLM_EINVAL
 int check_start(const int8_t *start, int C, int L, int q, uint32_t allowed, const uint8_t *fixed);
+// flags [q] (NULL: every state) -> the bit mask of the states that may be drawn; PLM_EINVAL when there is none
+int allowed_mask(int q, const uint8_t *flags, uint32_t *out);
+
+// the two words of a seed, as the kernels take them
+struct Seed {
+    uint32_t lo, hi;
+    explicit Seed(uint64_t seed) : lo((uint32_t)(seed & 0xFFFFFFFFu)), hi((uint32_t)(seed >> 32)) {}
+};
 
 // PLM_OK and the plan, or PLM_EDEVICE / PLM_EUNSUPPORTED / PLM_EINVAL (a PLM_SAMPLE_TILE or PLM_SAMPLE_JC without a
 // valid plan) with the message recorded
@@ -89,5 +98,32 @@ hipError_t launch(void (*kern)(P...), unsigned grid, unsigned block, const Sweep
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), p.lds, st, args...);
     return hipGetLastError();
 }
+
+// the launch of either form over C chains: a workgroup of the tiled form is a tile of chains, one of the direct form
+// 256 lanes in groups of qp lanes per chain
+template <typename... P, typename... A>
+hipError_t launch_tiled(void (*kern)(P...), int tile, int C, const SweepPlan &p, hipStream_t st, A... args) {
+    return launch(kern, (unsigned)((C + tile - 1) / tile), (unsigned)tile, p, st, args...);
+}
+template <typename... P, typename... A>
+hipError_t launch_direct(void (*kern)(P...), int qp, int C, const SweepPlan &p, hipStream_t st, A... args) {
+    const int cpw = 256 / qp;                    // chains per workgroup
+    return launch(kern, (unsigned)((C + cpw - 1) / cpw), 256u, p, st, args...);
+}
+
+// The model of a call on the device: the canonical vector and the table expanded from it.  Two allocations, because an
+// entry point's own buffers may sit between them, and the order decides which allocation fails first.
+struct DeviceModel {
+    const int L, q;
+    float *canon = nullptr;
+    float4 *W = nullptr;
+    DeviceModel(int L_, int q_) : L(L_), q(q_) {}
+    int alloc_canon(DeviceBuffers &mem) { return mem.alloc(&canon, (size_t)plm_n_canon(L, q)); }
+    int alloc_table(DeviceBuffers &mem) { return mem.alloc(&W, table_float4(L, q)); }
+    hipError_t upload(hipStream_t st, const float *x_canonical) const {
+        return hipMemcpyAsync(canon, x_canonical, (size_t)plm_n_canon(L, q) * sizeof(float), hipMemcpyHostToDevice, st);
+    }
+    hipError_t expand(hipStream_t st) const { return gibbs::expand(st, canon, L, q, W); }
+};
 
 }  // namespace gibbs

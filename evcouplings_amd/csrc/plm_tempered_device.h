@@ -15,7 +15,8 @@
 //   void write(chain, E)               the chain's scalars back to global memory (chain < C)
 //
 // The bodies are whole kernels on purpose: cut into one function per site update, with U passed as an array, the
-// tiled form took up to 82 registers more (the table in section 9.10).  The pipeline stays the macro over named locals.
+// tiled form took up to 82 registers more (the table in section 9.10).  The pipeline stays the macro over named locals,
+// and so is the frame around the site loop, which the bodies share with k_gibbs* and k_anneal* (plm_gibbs_device.h).
 // The kernels run at the limit of the scalar registers (106, with up to 480 spilled to lanes), so what a policy does
 // not need must not be computed for it: begin takes C and not the comparison, which would stay live in a register
 // pair to the last line for a policy that ignores it, and the tiled form opens in the statement order each kernel had
@@ -39,41 +40,12 @@ __device__ __forceinline__ float field_plus_scaled(float h, float beta, float u)
     return h + p;
 }
 
-// U_a of a state known only at run time, as a chain of selects over the NV 4 registers (an indexed array would live in
-// scratch memory)
-template <int NV>
-__device__ __forceinline__ float pick_state(const float4 *U, int a) {
-    float r = 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-        r = a == 4 * v + 0 ? U[v].x : r;
-        r = a == 4 * v + 1 ? U[v].y : r;
-        r = a == 4 * v + 2 ? U[v].z : r;
-        r = a == 4 * v + 3 ? U[v].w : r;
-    }
-    return r;
-}
-
-// The three passes a launch of the tiled form may open with, over the locals of tempered_tile by name: the start rule
-// (one draw per site of softmax h_i), the states of the tile from global memory, and the measuring pass (no draws;
-// every pair is met from both of its sites)
-#define TS_DRAW_START()                                                                                        \
-    for (int i = 0; i < L; i++) {                                                                              \
-        float4 Hi[NV];                                                                                         \
-        _Pragma("unroll") for (int v = 0; v < NV; v++) Hi[v] = H[i * NV + v];                                  \
-        const int a = draw_state<NV>(Hi, q, allowed, 1.0f, philox_word0((uint32_t)chain, 0u, GS_START_SWEEP,   \
-                                                                        (uint32_t)i, seed_lo, seed_hi));       \
-        xs[((i >> 2) * TILE + tid) * 4 + (i & 3)] = (uint8_t)a;                                                \
-    }
-#define TS_LOAD_STATES()                                                                                       \
-    for (int k = tid; k < n_here * L; k += TILE) {                                                             \
-        const int c = k / L, j = k - c * L;                                                                    \
-        xs[((j >> 2) * TILE + c) * 4 + (j & 3)] = (uint8_t)states[(int64_t)c0 * L + k];                        \
-    }
+// The measuring pass a launch of the tiled form may open with, over the locals of the frame by name (no draws; every
+// pair is met from both of its sites)
 #define TS_MEASURE()                                                                                           \
     for (int i = 0; i < L; i++) {                                                                              \
         GS_SITE_U(make_float4(0.f, 0.f, 0.f, 0.f))                                                             \
-        E += (double)pick_state<NV>(U, xs[((i >> 2) * TILE + tid) * 4 + (i & 3)]);                             \
+        E += (double)pick_state<NV>(U, xs[GS_XS(i, tid)]);                                                     \
     }                                                                                                          \
     E *= 0.5;
 
@@ -84,32 +56,19 @@ template <int NV, int TILE, typename Policy>
 __device__ __forceinline__ void tempered_tile(const float4 *__restrict__ W, int L, int q, int C, int JC, uint32_t allowed,
                                               uint32_t seed_lo, uint32_t seed_hi, int8_t *__restrict__ states /* [C][L] */,
                                               Policy P) {
-    constexpr int NVP = (NV % 2 == 0) ? NV + 1 : NV;
-    extern __shared__ float4 lds4[];
-    const int tid = threadIdx.x;
-    const int L4 = (L + 3) >> 2;
-    const int c0 = blockIdx.x * TILE;
-    const int chain = c0 + tid;
-    const int n_here = min(TILE, C - c0);
-    const int buf_f4 = JC * q * NVP;
-    float4 *stage = lds4;
-    uint8_t *xs = (uint8_t *)(lds4 + 2 * buf_f4);
-    uint32_t *xw = (uint32_t *)xs;
-    const float4 *H = W + (int64_t)L * L * q * NV;
-    const int n_chunks = (L + JC - 1) / JC;
-    const int row4 = q * NV;
-    uint32_t g = 0;
+    GS_TILE_FRAME()
+    GS_TILE_PIPE()
     const int mode = P.start_mode();
     P.begin(chain, C);
 
-    for (int k = tid; k < L4 * TILE; k += TILE) xw[k] = 0u;
+    GS_ZERO_STATES()
     __syncthreads();
     double E = 0.0;
     if constexpr (Policy::three_start_modes) {             // states, barrier, E
         if (mode == PT_START_RULE) {
-            TS_DRAW_START()
+            GS_DRAW_START(1.0f)
         } else {
-            TS_LOAD_STATES()
+            GS_LOAD_STATES(states)
         }
         __syncthreads();
         if (mode == PT_CONTINUE) {
@@ -118,11 +77,11 @@ __device__ __forceinline__ void tempered_tile(const float4 *__restrict__ W, int 
             TS_MEASURE()
         }
     } else if (mode == PT_START_RULE) {                    // two modes: the start with its E, or the continuation
-        TS_DRAW_START()
+        GS_DRAW_START(1.0f)
         __syncthreads();
         TS_MEASURE()
     } else {
-        TS_LOAD_STATES()
+        GS_LOAD_STATES(states)
         if (chain < C) P.read(chain, E);
         __syncthreads();
     }
@@ -143,7 +102,7 @@ __device__ __forceinline__ void tempered_tile(const float4 *__restrict__ W, int 
                     arg[v].z = field_plus_scaled(hv.z, beta, U[v].z);
                     arg[v].w = field_plus_scaled(hv.w, beta, U[v].w);
                 }
-                const int at = ((i >> 2) * TILE + tid) * 4 + (i & 3);
+                const int at = GS_XS(i, tid);
                 const int a_old = xs[at];
                 const int a = draw_state<NV>(arg, q, allowed, 1.0f,
                                              philox_word0((uint32_t)chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
@@ -153,10 +112,7 @@ __device__ __forceinline__ void tempered_tile(const float4 *__restrict__ W, int 
         }
     }
     __syncthreads();
-    for (int k = tid; k < n_here * L; k += TILE) {
-        const int c = k / L, j = k - c * L;
-        states[(int64_t)c0 * L + k] = (int8_t)xs[((j >> 2) * TILE + c) * 4 + (j & 3)];
-    }
+    GS_STORE_STATES(states)
     if (chain < C) P.write(chain, E);
 }
 
@@ -167,44 +123,20 @@ template <int QP, typename Policy>
 __device__ __forceinline__ void tempered_direct(const float *__restrict__ Wf, int L, int q, int QS, int C,
                                                 uint32_t allowed, uint32_t seed_lo, uint32_t seed_hi,
                                                 int8_t *__restrict__ states, Policy P) {
-    constexpr int CPW = 256 / QP;
-    extern __shared__ float4 lds4[];
-    uint8_t *xs = (uint8_t *)lds4;
-    const int tid = threadIdx.x, a = tid % QP, cl = tid / QP;
-    const int lane0 = (tid & 63) & ~(QP - 1);              // the group's first lane within the wave
-    const int Lp = (L + 3) & ~3;
-    const int c0 = blockIdx.x * CPW;
-    const int chain = c0 + cl;
-    const int n_here = min(CPW, C - c0);
-    const float *Hf = Wf + (int64_t)L * L * q * QS;
-    uint8_t *xc = xs + cl * Lp;
-    // U_a = sum_{j != i} J_ij(a, x_j) of the group's chain in float32, j = 0 .. L-1, from zero
-    const auto site_u = [&](int i) {
-        const float *Wi = Wf + (int64_t)i * L * q * QS;
-        float U = 0.f;
-        for (int j = 0; j < L; j++) {
-            if (j == i) continue;
-            const int x = xc[j];
-            if (a < q) U += Wi[((int64_t)j * q + x) * QS + a];
-        }
+    GS_DIRECT_FRAME()
+    GS_DIRECT_XC()
+    const auto site_u = [&](int i) {                       // from zero; a lambda, as the kernels had it (section 9.14)
+        GS_DIRECT_SITE_U(0.f)
         return U;
     };
     const int mode = P.start_mode();
     P.begin(chain, C);
-    for (int k = tid; k < CPW * Lp; k += 256) xs[k] = 0;
+    GS_DIRECT_ZERO()
     __syncthreads();
     if (mode == PT_START_RULE) {
-        for (int i = 0; i < L; i++) {
-            const float Hi = a < q ? Hf[i * QS + a] : 0.f;
-            const int x = draw_group<QP>(Hi, a, q, allowed, 1.0f,
-                                         philox_word0((uint32_t)chain, 0u, GS_START_SWEEP, (uint32_t)i, seed_lo, seed_hi));
-            if (a == 0) xc[i] = (uint8_t)x;
-        }
+        GS_DIRECT_DRAW_START(1.0f)
     } else {
-        for (int k = tid; k < n_here * L; k += 256) {
-            const int c = k / L, j = k - c * L;
-            xs[c * Lp + j] = (uint8_t)states[(int64_t)c0 * L + k];
-        }
+        GS_DIRECT_LOAD(states)
     }
     __syncthreads();
     double E = 0.0;
@@ -232,10 +164,7 @@ __device__ __forceinline__ void tempered_direct(const float *__restrict__ Wf, in
         }
     }
     __syncthreads();
-    for (int k = tid; k < n_here * L; k += 256) {
-        const int c = k / L, j = k - c * L;
-        states[(int64_t)c0 * L + k] = (int8_t)xs[c * Lp + j];
-    }
+    GS_DIRECT_STORE(states)
     if (a == 0 && chain < C) P.write(chain, E);
 }
 

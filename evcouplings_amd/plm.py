@@ -116,6 +116,62 @@ def _canonical(hi, jij, L, q):
     return np.concatenate([hi, jij])
 
 
+def _potts_model(hi, jij, q):
+    """(hi, jij, L) of a model as the wrappers of the generative side take it: hi a float32 (L, q) matrix, jij float32
+    with the entries of the i<j blocks; a ValueError otherwise."""
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
+        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
+    L = hi.shape[0]
+    jij = np.ascontiguousarray(jij, dtype=np.float32)
+    if jij.size != L * (L - 1) // 2 * q * q:
+        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    return hi, jij, L
+
+
+def _chain_args(start, fixed, allowed, C_, L, q):
+    """(start, fixed, allowed) as the library takes them, each None or checked in that order: C_ x L int8 states, L and q
+    uint8 flags."""
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.int8)
+        if start.shape != (C_, L):
+            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8)
+        if fixed.shape != (L,):
+            raise ValueError("fixed must hold L = %d flags" % L)
+    if allowed is not None:
+        allowed = np.ascontiguousarray(np.asarray(allowed).astype(bool), dtype=np.uint8)
+        if allowed.shape != (q,):
+            raise ValueError("allowed must hold q = %d flags" % q)
+    return start, fixed, allowed
+
+
+def _progress(done, total):
+    return int(done), int(total)
+
+
+def _stop_callback(functype, callback, convert=_progress):
+    """(cb, reraise): the ctypes callback of type functype that passes convert(the library's arguments without the user
+    pointer) to callback and answers 1 (stop) for a true value, and reraise(), to be called after the library returns.
+    An exception must not cross the C frames: it stops the call and reraise() raises it again.  callback None: a NULL
+    function pointer."""
+    failure = []
+
+    def _cb(*args):
+        try:
+            return 1 if callback(*convert(*args[:-1])) else 0
+        except BaseException as exc:
+            failure.append(exc)
+            return 1
+
+    def reraise():
+        if failure:
+            raise failure[0]
+
+    return (functype(_cb) if callback is not None else functype()), reraise
+
+
 def alignment_stats(msa, gap_state=0, query=None, device=0):
     """Per-sequence gap counts, per-column gap counts and (if `query` is given) identities of every sequence to the
     query, as int32 arrays (n,), (L,), (n,) -- the raw counts behind Alignment.count(gap, axis=...) and
@@ -288,34 +344,16 @@ def sample(hi, jij, q, n_chains, burn_in=10, n_snapshots=1, thin=1, beta=1.0, se
     Returns (samples int8 [K, C, L], energies float64 [K, C, 3] = (H, H_J, H_h) at beta = 1, or None).
     """
     q, C_, K = int(q), int(n_chains), int(n_snapshots)
-    hi = np.ascontiguousarray(hi, dtype=np.float32)
-    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
-        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
-    L = hi.shape[0]
-    jij = np.ascontiguousarray(jij, dtype=np.float32)
-    if jij.size != L * (L - 1) // 2 * q * q:
-        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    hi, jij, L = _potts_model(hi, jij, q)
     if C_ < 1 or K < 1 or int(burn_in) < 0 or int(thin) < 1:
         raise ValueError("need n_chains >= 1, n_snapshots >= 1, burn_in >= 0 and thin >= 1")
-    if start is not None:
-        start = np.ascontiguousarray(start, dtype=np.int8)
-        if start.shape != (C_, L):
-            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
-    if fixed is not None:
-        fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8)
-        if fixed.shape != (L,):
-            raise ValueError("fixed must hold L = %d flags" % L)
-    if allowed is not None:
-        allowed = np.ascontiguousarray(np.asarray(allowed).astype(bool), dtype=np.uint8)
-        if allowed.shape != (q,):
-            raise ValueError("allowed must hold q = %d flags" % q)
+    start, fixed, allowed = _chain_args(start, fixed, allowed, C_, L, q)
     lib = _lib.load()
     opts = _lib.PlmSampleOpts(C_, int(burn_in), K, int(thin), float(beta), int(seed) & 0xFFFFFFFFFFFFFFFF,
                               _ptr(start), _ptr(fixed), _ptr(allowed))
     samples = np.zeros((K, C_, L), dtype=np.int8)
     en = np.zeros((K, C_, 3)) if energies else None
-    x = np.concatenate([hi.reshape(L * q), jij.reshape(-1)])
-    check(lib.plm_sample(L, q, _ptr(x), C.byref(opts), int(device), None, _ptr(samples), _ptr(en)))
+    check(lib.plm_sample(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, _ptr(samples), _ptr(en)))
     return samples, en
 
 
@@ -352,13 +390,7 @@ def log_partition(hi, jij, q, n_chains=4096, n_temps=1000, sweeps_per_temp=1, be
     H(x_c) over the normalised weights, H from `hamiltonians` on the final states, and entropy = log_z - mean_energy.
     """
     q, C_ = int(q), int(n_chains)
-    hi = np.ascontiguousarray(hi, dtype=np.float32)
-    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
-        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
-    L = hi.shape[0]
-    jij = np.ascontiguousarray(jij, dtype=np.float32)
-    if jij.size != L * (L - 1) // 2 * q * q:
-        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    hi, jij, L = _potts_model(hi, jij, q)
     if betas is not None:
         betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
         if betas.size < 2:
@@ -371,19 +403,9 @@ def log_partition(hi, jij, q, n_chains=4096, n_temps=1000, sweeps_per_temp=1, be
     n_out = max(C_, 1)
     log_w, e_j, states = np.zeros(n_out), np.zeros(n_out), np.zeros((n_out, L), np.int8)
     res = _lib.PlmAisResult(0.0, 0.0, 0.0, 0.0, _ptr(log_w), _ptr(e_j), _ptr(states), 0, 0)
-    failure = []
-
-    def _cb(done, total, _user):
-        try:
-            return 1 if callback(int(done), int(total)) else 0
-        except BaseException as exc:     # an exception must not cross the C frames
-            failure.append(exc)
-            return 1
-
-    cb = _lib.AIS_CB(_cb) if callback is not None else _lib.AIS_CB()
+    cb, reraise = _stop_callback(_lib.AIS_CB, callback)
     check(lib.plm_ais(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb, None, C.byref(res)))
-    if failure:
-        raise failure[0]
+    reraise()
     out = dict(log_z=float(res.log_z), log_z0=float(res.log_z0), log_z_se=float(res.log_z_se), ess=float(res.ess),
                log_w=log_w, e_j=e_j, states=states, steps_done=int(res.steps_done), status=BM_STATUS[int(res.status)])
     last = 1.0 if betas is None else float(betas[-1])
@@ -437,13 +459,7 @@ def parallel_tempering(hi, jij, q, n_ladders, betas, burn_in=10, n_snapshots=1, 
     "interrupted": snapshots not yet taken are zero then).
     """
     q, C_, K = int(q), int(n_ladders), int(n_snapshots)
-    hi = np.ascontiguousarray(hi, dtype=np.float32)
-    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
-        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
-    L = hi.shape[0]
-    jij = np.ascontiguousarray(jij, dtype=np.float32)
-    if jij.size != L * (L - 1) // 2 * q * q:
-        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    hi, jij, L = _potts_model(hi, jij, q)
     betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
     R = betas.size
     if R < 1:
@@ -477,19 +493,9 @@ def parallel_tempering(hi, jij, q, n_ladders, betas, burn_in=10, n_snapshots=1, 
     walkers, rungs, walker_e = np.zeros((Cn * R, L), np.int8), np.zeros(Cn * R, np.int32), np.zeros(Cn * R)
     res = _lib.PlmPtResult(_ptr(samples), _ptr(e_j), _ptr(accepts) if R > 1 else None,
                            _ptr(attempts) if R > 1 else None, _ptr(walkers), _ptr(rungs), _ptr(walker_e), 0, 0)
-    failure = []
-
-    def _cb(done, total, _user):
-        try:
-            return 1 if callback(int(done), int(total)) else 0
-        except BaseException as exc:     # an exception must not cross the C frames
-            failure.append(exc)
-            return 1
-
-    cb = _lib.PT_CB(_cb) if callback is not None else _lib.PT_CB()
+    cb, reraise = _stop_callback(_lib.PT_CB, callback)
     check(lib.plm_pt(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb, None, C.byref(res)))
-    if failure:
-        raise failure[0]
+    reraise()
     rows = samples.reshape(-1, L)
     if L > 1:
         en = hamiltonians(rows, q, hi, jij, device=device)
@@ -593,31 +599,14 @@ def anneal(hi, jij, q, n_chains, betas=None, n_steps=100, sweeps_per_step=1, max
     ("converged" or "interrupted").
     """
     q, C_ = int(q), int(n_chains)
-    hi = np.ascontiguousarray(hi, dtype=np.float32)
-    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
-        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
-    L = hi.shape[0]
-    jij = np.ascontiguousarray(jij, dtype=np.float32)
-    if jij.size != L * (L - 1) // 2 * q * q:
-        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    hi, jij, L = _potts_model(hi, jij, q)
     if betas is None:
         betas = annealing_schedule(int(n_steps))
     betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
     K = betas.size
     if C_ < 1:
         raise ValueError("need n_chains >= 1")
-    if start is not None:
-        start = np.ascontiguousarray(start, dtype=np.int8)
-        if start.shape != (C_, L):
-            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
-    if fixed is not None:
-        fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8)
-        if fixed.shape != (L,):
-            raise ValueError("fixed must hold L = %d flags" % L)
-    if allowed is not None:
-        allowed = np.ascontiguousarray(np.asarray(allowed).astype(bool), dtype=np.uint8)
-        if allowed.shape != (q,):
-            raise ValueError("allowed must hold q = %d flags" % q)
+    start, fixed, allowed = _chain_args(start, fixed, allowed, C_, L, q)
     lib = _lib.load()
     opts = _lib.PlmAnnealOpts(C_, K, int(sweeps_per_step), int(max_greedy), int(first_sweep) & 0xFFFFFFFF,
                               int(steps_per_launch), _ptr(betas) if K else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -628,19 +617,9 @@ def anneal(hi, jij, q, n_chains, betas=None, n_steps=100, sweeps_per_step=1, max
                best_energies=np.zeros((C_, 3)) if energies else None)
     res = _lib.PlmAnnealResult(*[_ptr(out[k]) for k in ("states", "gain", "best", "best_gain", "best_at", "last_move",
                                                         "converged", "energies", "best_energies")], 0, 0)
-    failure = []
-
-    def _cb(done, total, _user):
-        try:
-            return 1 if callback(int(done), int(total)) else 0
-        except BaseException as exc:     # an exception must not cross the C frames
-            failure.append(exc)
-            return 1
-
-    cb = _lib.ANNEAL_CB(_cb) if callback is not None else _lib.ANNEAL_CB()
+    cb, reraise = _stop_callback(_lib.ANNEAL_CB, callback)
     check(lib.plm_anneal(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb, None, C.byref(res)))
-    if failure:
-        raise failure[0]
+    reraise()
     out["converged"] = out["converged"].astype(bool)
     out["steps_done"] = int(res.steps_done)
     out["status"] = BM_STATUS[int(res.status)]
@@ -678,14 +657,8 @@ def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, 
     "interrupted").  The result is bitwise reproducible.
     """
     q, C_, E = int(q), int(n_chains), int(n_epochs)
-    hi = np.ascontiguousarray(hi, dtype=np.float32)
-    if hi.ndim != 2 or hi.shape[1] != q or hi.shape[0] < 1:
-        raise ValueError("hi must be an (L, q) matrix with q = %d" % q)
-    L = hi.shape[0]
-    n_j = L * (L - 1) // 2 * q * q
-    jij = np.ascontiguousarray(jij, dtype=np.float32)
-    if jij.size != n_j:
-        raise ValueError("jij has %d entries, expected the %d i<j blocks of %d x %d" % (jij.size, L * (L - 1) // 2, q, q))
+    hi, jij, L = _potts_model(hi, jij, q)
+    n_j = jij.size
     fi = np.ascontiguousarray(fi, dtype=np.float32)
     if fi.shape != (L, q):
         raise ValueError("fi must be an (L, q) = (%d, %d) matrix" % (L, q))
@@ -697,10 +670,7 @@ def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, 
     for name, v in (("lr", lr), ("lambda_h", lambda_h), ("lambda_j", lambda_j), ("tol", tol)):
         if not (float(v) >= 0.0 and np.isfinite(float(v))):
             raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
-    if start is not None:
-        start = np.ascontiguousarray(start, dtype=np.int8)
-        if start.shape != (C_, L):
-            raise ValueError("start must be an (n_chains, L) = (%d, %d) matrix of states" % (C_, L))
+    start = _chain_args(start, None, None, C_, L, q)[0]
     lib = _lib.load()
     opts = _lib.PlmBmOpts(C_, E, int(sweeps_per_epoch), int(first_epoch), float(lr), int(lr_decay_after), float(lambda_h),
                           float(lambda_j), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(start))
@@ -709,20 +679,10 @@ def bm_fit(fi, fij, q, hi, jij, n_chains, n_epochs, sweeps_per_epoch=2, lr=0.5, 
     chains = np.zeros((C_, L), np.int8)
     trace = np.zeros((E, 4))
     res = _lib.PlmBmResult(_ptr(x), _ptr(pi), _ptr(pij), _ptr(chains), _ptr(trace), 0, 0)
-    failure = []
-
-    def _cb(epoch, d_i, d_ij, rms, lr_g, _user):
-        try:
-            return 1 if callback(int(epoch), d_i, d_ij, rms, lr_g) else 0
-        except BaseException as exc:     # an exception must not cross the C frames
-            failure.append(exc)
-            return 1
-
-    cb = _lib.BM_EPOCH_CB(_cb) if callback is not None else _lib.BM_EPOCH_CB()
+    cb, reraise = _stop_callback(_lib.BM_EPOCH_CB, callback, lambda epoch, *errors: (int(epoch),) + errors)
     check(lib.plm_bm_fit(L, q, _ptr(fi), _ptr(fij), _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, cb,
                          None, C.byref(res)))
-    if failure:
-        raise failure[0]
+    reraise()
     done = int(res.epochs_done)
     rows = done if res.status == _lib.STATUS_MAXITER else done + 1
     return dict(hi=x[:L * q].reshape(L, q).copy(), jij=x[L * q:].reshape(L * (L - 1) // 2, q, q).copy(), pi=pi, pij=pij,
