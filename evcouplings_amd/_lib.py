@@ -262,6 +262,15 @@ SYMBOLS = [
     ("plm_ctx_field_position", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmFieldBuffers)]),
     ("plm_ctx_field_solve", C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmFieldSolve), _P,
                                       C.c_int64]),
+    ("plm_lbfgs_gram", C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                 C.c_int, _P, _P, _P, _P]),
+    ("plm_lbfgs_direction", C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_double, _P, _P,
+                                      C.c_float, C.c_int, _P, _P]),
+    ("plm_lbfgs_multidot", C.c_int, [C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_uint32, C.c_uint64,
+                                     C.c_int, _P]),
+    ("plm_lbfgs_dots", C.c_int, [C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, C.c_int, _P]),
+    ("plm_lbfgs_lincomb", C.c_int, [C.c_int64, C.c_float, _P, C.c_float, _P, C.c_int, _P]),
+    ("plm_ctx_precond_diagonal", C.c_int, [_P, _P]),
     ("plm_rccl_probe", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int, _P]),
     ("plm_rccl_probe_local", C.c_int, [C.c_int32, C.c_int, _P]),
     ("plm_lbfgs_coefficients", None, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P,

@@ -1356,6 +1356,59 @@ int plm_ctx_eval(plm_ctx_t *c, double *fx_out, double *nll_out) {
     return PLM_OK;
 }
 
+// ---- pieces of plm_ctx_optimize that the diagnostic entries (plm_lbfgs_gram, plm_lbfgs_direction,
+// plm_ctx_precond_diagonal) run as well: one definition of the basis order, the flags and the H0 diagonal ----------
+// c->dinv = 1 / (Hessian diagonal of the independent-site model at the start point), native layout (k_precond_*)
+static int ctx_build_dinv(plm_ctx_t *c) {
+    const PlmDims &d = c->d;
+    if (!c->dinv) PLM_TRY(plm_dalloc(&c->dinv, (size_t)d.n_local));
+    const size_t lq = (size_t)d.L * d.Q;
+    std::vector<float> fv(2 * lq, 0.f);
+    const int a0 = d.gap_mode;
+    for (int i = 0; i < d.L; i++) {
+        double tot = 0;
+        for (int a = a0; a < d.Qc; a++) tot += (double)c->h_fi[i * d.Qc + a] + 1.0 / c->n_eff;
+        for (int a = a0; a < d.Qc; a++) {
+            const double pa = ((double)c->h_fi[i * d.Qc + a] + 1.0 / c->n_eff) / tot;   // the start point's P_i(a)
+            fv[i * d.Q + a] = c->h_fi[i * d.Qc + a];
+            fv[lq + i * d.Q + a] = (float)(pa * (1.0 - pa));
+        }
+    }
+    // staged through the gradient buffer's tail?  no: a small dedicated upload into canon (free during optimize)
+    PLM_HIP(hipMemcpyAsync(c->canon, fv.data(), sizeof(float) * fv.size(), hipMemcpyHostToDevice, c->st));
+    PLM_HIP(plm_launch_precond(d, c->canon, (float)c->n_eff, (float)c->prob.lambda_h, (float)c->prob.lambda_j,
+                               c->dinv, c->st));
+    PLM_HIP(hipStreamSynchronize(c->st));   // fv leaves scope
+    return PLM_OK;
+}
+// Basis and flags of the Gram pass (queries s_new, y_new, g): S[0..nst), Y[0..nst), g, g.  Products in the H0 metric:
+// the Y's and the first g on the basis side (wb), y_new and g on the query side (wq); the second g stays unweighted
+// (g.g for the stop rule).
+static void lbfgs_gram_basis(const float *S, const float *Y, const float *g, int64_t n, int nst, PlmVecList *B,
+                             unsigned long long *wb_out, unsigned *wq_out) {
+    B->n = 0;
+    for (int i = 0; i < nst; i++) B->v[B->n++] = S + (size_t)i * n;
+    unsigned long long wb = 0;
+    for (int i = 0; i < nst; i++) { wb |= 1ull << B->n; B->v[B->n++] = Y + (size_t)i * n; }
+    wb |= 1ull << B->n;
+    B->v[B->n++] = g;
+    B->v[B->n++] = g;
+    *wb_out = wb;
+    *wq_out = 6u;
+}
+// Basis and coefficients of the direction p = sum cs[j] s_j + D^-1 (sum cy[j] y_j + cg g) over the LIVE pairs, the
+// `stored` ring slots before `end`, newest first; returns the index of the first vector under D^-1.
+static int lbfgs_direction_basis(const float *S, const float *Y, const float *g, int64_t n, int m, int stored, int end,
+                                 const double *cs, const double *cy, double cg, PlmVecList *B, PlmCoefList *C) {
+    B->n = 0;
+    for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B->v[B->n] = S + (size_t)j * n; C->c[B->n++] = (float)cs[j]; }
+    const int first_weighted = B->n;
+    for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B->v[B->n] = Y + (size_t)j * n; C->c[B->n++] = (float)cy[j]; }
+    B->v[B->n] = g;
+    C->c[B->n++] = (float)cg;
+    return first_weighted;
+}
+
 // L-BFGS with a More'-Thuente line search; vectors stay in HBM, only scalars cross PCIe.
 // Defaults follow libLBFGS (m = 6, ftol 1e-4, gtol 0.9, <= 20 trial steps), which plmc bundles
 // [recollection, SURVEY.md App. C.4].  The two-loop recursion (Nocedal 1980) is evaluated in
@@ -1394,26 +1447,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // from the single-site frequencies).  The recursion only ever needs s.y, s.g and the D^-1-weighted products of
     // {y_j, g}.  Opt-in (PLM_FLAG_PRECOND): measured to need MORE iterations than the scalar H0 at L = 300.
     const bool precond = (c->prob.flags & PLM_FLAG_PRECOND) && !c->h_fi.empty();
-    if (precond) {
-        if (!c->dinv) PLM_TRY(plm_dalloc(&c->dinv, (size_t)n));
-        const size_t lq = (size_t)d.L * d.Q;
-        std::vector<float> fv(2 * lq, 0.f);
-        const int a0 = d.gap_mode;
-        for (int i = 0; i < d.L; i++) {
-            double tot = 0;
-            for (int a = a0; a < d.Qc; a++) tot += (double)c->h_fi[i * d.Qc + a] + 1.0 / c->n_eff;
-            for (int a = a0; a < d.Qc; a++) {
-                const double pa = ((double)c->h_fi[i * d.Qc + a] + 1.0 / c->n_eff) / tot;   // the start point's P_i(a)
-                fv[i * d.Q + a] = c->h_fi[i * d.Qc + a];
-                fv[lq + i * d.Q + a] = (float)(pa * (1.0 - pa));
-            }
-        }
-        // staged through the gradient buffer's tail?  no: a small dedicated upload into canon (free during optimize)
-        PLM_HIP(hipMemcpyAsync(c->canon, fv.data(), sizeof(float) * fv.size(), hipMemcpyHostToDevice, c->st));
-        PLM_HIP(plm_launch_precond(d, c->canon, (float)c->n_eff, (float)c->prob.lambda_h, (float)c->prob.lambda_j,
-                                   c->dinv, c->st));
-        PLM_HIP(hipStreamSynchronize(c->st));   // fv leaves scope
-    }
+    if (precond) PLM_TRY(ctx_build_dinv(c));
     const float *dinv = precond ? c->dinv : nullptr;
     // Gram matrix pieces, indexed by history slot: SY[i][j] = s_i.y_j, YDY[i][j] = y_i.D^-1 y_j, Sg = s_i.g,
     // YDg = y_i.D^-1 g, gDg = g.D^-1 g, gg = g.g (stop rule)
@@ -1441,12 +1475,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                                dginit);
         PlmVecList B;
         PlmCoefList C;
-        B.n = 0;
-        for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B.v[B.n] = S + (size_t)j * n; C.c[B.n++] = (float)cs[j]; }
-        const int first_weighted = B.n;
-        for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B.v[B.n] = Y + (size_t)j * n; C.c[B.n++] = (float)cy[j]; }
-        B.v[B.n] = c->g;
-        C.c[B.n++] = (float)cg;
+        const int first_weighted = lbfgs_direction_basis(S, Y, c->g, n, m, stored, end, cs.data(), cy.data(), cg, &B, &C);
         if (trial) PLM_HIP(plm_launch_multiaxpy_trial(c->dir, B, C, n, dinv, first_weighted, xacc, stp0, trial, c->st));
         else PLM_HIP(plm_launch_multiaxpy(c->dir, B, C, n, dinv, first_weighted, c->st));
         return PLM_OK;
@@ -1589,17 +1618,10 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             // the new pair goes into slot `end`; queries and basis of the Gram pass (rows for s, y, g)
             float *s_new = S + (size_t)end * n, *y_new = Y + (size_t)end * n;
             const int nst = std::min(m, stored + 1);
-            PlmVecList Qv, B;
-            Qv.n = 3;
-            Qv.v[0] = s_new; Qv.v[1] = y_new; Qv.v[2] = c->g;       // c->g: the buffer the trial gradients land in
-            B.n = 0;
-            for (int i = 0; i < nst; i++) B.v[B.n++] = S + (size_t)i * n;
-            unsigned long long wb = 0;                    // basis vectors that enter products in the H0 metric: Y, g
-            for (int i = 0; i < nst; i++) { wb |= 1ull << B.n; B.v[B.n++] = Y + (size_t)i * n; }
-            wb |= 1ull << B.n;
-            B.v[B.n++] = c->g;
-            B.v[B.n++] = c->g;                            // once more, unweighted: g.g for the stop rule
-            const unsigned wq = 6u;                       // queries y_new and g
+            PlmVecList B;
+            unsigned long long wb;                        // basis vectors that enter products in the H0 metric: Y, g
+            unsigned wq;                                  // queries y_new and g
+            lbfgs_gram_basis(S, Y, c->g, n, nst, &B, &wb, &wq);      // c->g: the buffer the trial gradients land in
             double gh2_trial = 0;
             // objective + gradient at the trial point c->x, and with it everything the NEXT direction needs
             auto evaluate_trial = [&]() -> int {
@@ -2023,6 +2045,194 @@ int plm_ctx_field_solve(plm_ctx_t *c, double tol, int32_t vp_c_prev, int32_t inv
     memcpy(res->hist, S.hist, sizeof res->hist);
     memcpy(res->quiet, S.quiet, sizeof res->quiet);
     return PLM_OK;
+}
+
+// ---- the L-BFGS vector kernels and the H0 diagonal, test-facing (include/plm_hip.h: diagnostic) --------------------
+// One-shot entries on host vectors: no context.  Before each launch the dot scratch (sized as plm_ctx_create sizes it)
+// and every output buffer are filled with 0xFF bytes (NaN), so what the kernels do not write comes back as NaN.
+extern "C++" {
+namespace {
+struct LbfgsProbe {
+    DeviceBuffers mem;
+    double *scratch = nullptr;
+    static constexpr size_t n_scratch = (size_t)4 * PLM_MAX_BASIS * PLM_DOT_BLOCKS;
+    template <typename T> int upload(T **p, const T *host, size_t n_elems) {
+        PLM_TRY(mem.alloc(p, n_elems));
+        PLM_HIP(hipMemcpy(*p, host, sizeof(T) * n_elems, hipMemcpyHostToDevice));
+        return PLM_OK;
+    }
+    template <typename T> int nan_out(T **p, size_t n_elems) {
+        PLM_TRY(mem.alloc(p, n_elems));
+        PLM_HIP(hipMemset(*p, 0xFF, sizeof(T) * n_elems));
+        return PLM_OK;
+    }
+    int nan_scratch() {
+        if (!scratch) PLM_TRY(mem.alloc(&scratch, n_scratch));
+        PLM_HIP(hipMemset(scratch, 0xFF, sizeof(double) * n_scratch));
+        return PLM_OK;
+    }
+    template <typename T> int download(T *host, const T *p, size_t n_elems) {
+        PLM_HIP(hipMemcpy(host, p, sizeof(T) * n_elems, hipMemcpyDeviceToHost));
+        return PLM_OK;
+    }
+};
+int lbfgs_probe_length(int64_t n) {
+    if (n <= 0 || (n & 3)) return fail(PLM_EINVAL, "the vector length must be a positive multiple of 4, not %lld", (long long)n);
+    return PLM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int plm_lbfgs_gram(int64_t n, int64_t nh, int32_t m, int32_t end, int32_t nst, const float *S, const float *Y,
+                   const float *x, const float *xp, const float *g, const float *gp, const float *dir, const float *dinv,
+                   int device, float *s_new, float *y_new, double *md, double *ex) {
+    if (!S || !Y || !x || !xp || !g || !gp || !dir || !s_new || !y_new || !md || !ex) return fail(PLM_EINVAL, "NULL argument");
+    PLM_TRY(lbfgs_probe_length(n));
+    if (nh < 0 || (nh & 3) || nh > n) return fail(PLM_EINVAL, "nh must be a multiple of 4 in 0..n, not %lld", (long long)nh);
+    if (m < 1 || nst < 1 || nst > m) return fail(PLM_EINVAL, "need 1 <= nst <= m (m = %d, nst = %d)", (int)m, (int)nst);
+    if (2 * nst + 2 > PLM_MAX_BASIS) return fail(PLM_EINVAL, "%d basis vectors, at most %d", 2 * (int)nst + 2, PLM_MAX_BASIS);
+    if (end < 0 || end >= m) return fail(PLM_EINVAL, "ring slot %d outside 0..%d", (int)end, (int)m - 1);
+    if (end >= nst) return fail(PLM_EINVAL, "the new pair's slot %d is not among the %d slots of the basis", (int)end, (int)nst);
+    PLM_TRY(check_device(device));
+    LbfgsProbe P;
+    float *dS, *dY, *dx, *dxp, *dg, *dgp, *ddir, *ddinv = nullptr;
+    double *dmd, *dex;
+    const size_t nn = (size_t)n;
+    PLM_TRY(P.upload(&dS, S, (size_t)nst * nn));      // slots >= nst are in no basis
+    PLM_TRY(P.upload(&dY, Y, (size_t)nst * nn));
+    PLM_TRY(P.upload(&dx, x, nn));
+    PLM_TRY(P.upload(&dxp, xp, nn));
+    PLM_TRY(P.upload(&dg, g, nn));
+    PLM_TRY(P.upload(&dgp, gp, nn));
+    PLM_TRY(P.upload(&ddir, dir, nn));
+    if (dinv) PLM_TRY(P.upload(&ddinv, dinv, nn));
+    PlmVecList B;
+    unsigned long long wb;
+    unsigned wq;
+    lbfgs_gram_basis(dS, dY, dg, n, nst, &B, &wb, &wq);
+    PLM_TRY(P.nan_out(&dmd, (size_t)3 * B.n + 1));
+    PLM_TRY(P.nan_out(&dex, 3));
+    PLM_TRY(P.nan_scratch());
+    float *ds_new = dS + (size_t)end * nn, *dy_new = dY + (size_t)end * nn;
+    PLM_HIP(plm_launch_sy_multidot(ds_new, dy_new, dx, dxp, dg, dgp, ddir, B, n, nh, P.scratch, dmd, dex, ddinv, wq, wb, nullptr));
+    PLM_HIP(hipDeviceSynchronize());
+    PLM_TRY(P.download(s_new, ds_new, nn));
+    PLM_TRY(P.download(y_new, dy_new, nn));
+    PLM_TRY(P.download(md, dmd, (size_t)3 * B.n + 1));
+    PLM_TRY(P.download(ex, dex, 3));
+    return PLM_OK;
+}
+
+int plm_lbfgs_direction(int64_t n, int32_t m, int32_t stored, int32_t end, const float *S, const float *Y, const float *g,
+                        const double *cs, const double *cy, double cg, const float *dinv, const float *xacc, float stp0,
+                        int device, float *dir, float *trial) {
+    if (!S || !Y || !g || !cs || !cy || !dir) return fail(PLM_EINVAL, "NULL argument");
+    if (trial && !xacc) return fail(PLM_EINVAL, "a trial point needs xacc");
+    PLM_TRY(lbfgs_probe_length(n));
+    if (m < 1 || stored < 0 || stored > m) return fail(PLM_EINVAL, "need 0 <= stored <= m (m = %d, stored = %d)", (int)m, (int)stored);
+    if (2 * stored + 1 > PLM_MAX_BASIS) return fail(PLM_EINVAL, "%d basis vectors, at most %d", 2 * (int)stored + 1, PLM_MAX_BASIS);
+    if (end < 0 || end >= m) return fail(PLM_EINVAL, "ring slot %d outside 0..%d", (int)end, (int)m - 1);
+    PLM_TRY(check_device(device));
+    LbfgsProbe P;
+    float *dS, *dY, *dg, *ddinv = nullptr, *dxacc = nullptr, *ddir, *dtrial = nullptr;
+    const size_t nn = (size_t)n;
+    PLM_TRY(P.upload(&dS, S, (size_t)m * nn));
+    PLM_TRY(P.upload(&dY, Y, (size_t)m * nn));
+    PLM_TRY(P.upload(&dg, g, nn));
+    if (dinv) PLM_TRY(P.upload(&ddinv, dinv, nn));
+    if (trial) PLM_TRY(P.upload(&dxacc, xacc, nn));
+    PLM_TRY(P.nan_out(&ddir, nn));
+    if (trial) PLM_TRY(P.nan_out(&dtrial, nn));
+    PlmVecList B;
+    PlmCoefList C;
+    const int first_weighted = lbfgs_direction_basis(dS, dY, dg, n, m, stored, end, cs, cy, cg, &B, &C);
+    if (trial) PLM_HIP(plm_launch_multiaxpy_trial(ddir, B, C, n, ddinv, first_weighted, dxacc, stp0, dtrial, nullptr));
+    else PLM_HIP(plm_launch_multiaxpy(ddir, B, C, n, ddinv, first_weighted, nullptr));
+    PLM_HIP(hipDeviceSynchronize());
+    PLM_TRY(P.download(dir, ddir, nn));
+    if (trial) PLM_TRY(P.download(trial, dtrial, nn));
+    return PLM_OK;
+}
+
+int plm_lbfgs_multidot(int64_t n, int32_t nv, const float *V, int32_t nq, const int32_t *q_index, int32_t nb,
+                       const int32_t *b_index, const float *dinv, uint32_t wq, uint64_t wb, int device, double *out) {
+    if (!V || !q_index || !b_index || !out) return fail(PLM_EINVAL, "NULL argument");
+    PLM_TRY(lbfgs_probe_length(n));
+    if (nv < 1) return fail(PLM_EINVAL, "no vectors");
+    if (nq < 1 || nq > 4) return fail(PLM_EINVAL, "%d queries, need 1..4", (int)nq);
+    if (nb < 1 || nb > PLM_MAX_BASIS) return fail(PLM_EINVAL, "%d basis vectors, need 1..%d", (int)nb, PLM_MAX_BASIS);
+    for (int k = 0; k < nq; k++)
+        if (q_index[k] < 0 || q_index[k] >= nv) return fail(PLM_EINVAL, "query %d names vector %d of %d", k, (int)q_index[k], (int)nv);
+    for (int k = 0; k < nb; k++)
+        if (b_index[k] < 0 || b_index[k] >= nv) return fail(PLM_EINVAL, "basis entry %d names vector %d of %d", k, (int)b_index[k], (int)nv);
+    PLM_TRY(check_device(device));
+    LbfgsProbe P;
+    float *dV, *ddinv = nullptr;
+    double *dout;
+    const size_t nn = (size_t)n;
+    PLM_TRY(P.upload(&dV, V, (size_t)nv * nn));
+    if (dinv) PLM_TRY(P.upload(&ddinv, dinv, nn));
+    PLM_TRY(P.nan_out(&dout, (size_t)nq * nb));
+    PLM_TRY(P.nan_scratch());
+    PlmVecList Qv, B;
+    Qv.n = nq;
+    for (int k = 0; k < nq; k++) Qv.v[k] = dV + (size_t)q_index[k] * nn;
+    B.n = nb;
+    for (int k = 0; k < nb; k++) B.v[k] = dV + (size_t)b_index[k] * nn;
+    PLM_HIP(plm_launch_multidot(Qv, B, n, P.scratch, dout, ddinv, wq, wb, nullptr));
+    PLM_HIP(hipDeviceSynchronize());
+    PLM_TRY(P.download(out, dout, (size_t)nq * nb));
+    return PLM_OK;
+}
+
+int plm_lbfgs_dots(int64_t stride, int32_t nv, const float *V, int32_t npairs, const int32_t *a_index,
+                   const int32_t *b_index, int64_t n, int device, double *out) {
+    if (!V || !a_index || !b_index || !out) return fail(PLM_EINVAL, "NULL argument");
+    PLM_TRY(lbfgs_probe_length(stride));
+    if (n < 0 || (n & 3) || n > stride) return fail(PLM_EINVAL, "n must be a multiple of 4 in 0..stride, not %lld", (long long)n);
+    if (nv < 1) return fail(PLM_EINVAL, "no vectors");
+    if (npairs < 1 || npairs > 4) return fail(PLM_EINVAL, "%d pairs, need 1..4", (int)npairs);
+    for (int k = 0; k < npairs; k++)
+        if (a_index[k] < 0 || a_index[k] >= nv || b_index[k] < 0 || b_index[k] >= nv)
+            return fail(PLM_EINVAL, "pair %d names vectors %d, %d of %d", k, (int)a_index[k], (int)b_index[k], (int)nv);
+    PLM_TRY(check_device(device));
+    LbfgsProbe P;
+    float *dV;
+    double *dout;
+    const size_t ns = (size_t)stride;
+    PLM_TRY(P.upload(&dV, V, (size_t)nv * ns));
+    PLM_TRY(P.nan_out(&dout, (size_t)npairs));
+    PLM_TRY(P.nan_scratch());
+    const float *a[4], *b[4];
+    for (int k = 0; k < npairs; k++) { a[k] = dV + (size_t)a_index[k] * ns; b[k] = dV + (size_t)b_index[k] * ns; }
+    PLM_HIP(plm_launch_dots(npairs, a, b, n, P.scratch, dout, nullptr));
+    PLM_HIP(hipDeviceSynchronize());
+    PLM_TRY(P.download(out, dout, (size_t)npairs));
+    return PLM_OK;
+}
+
+int plm_lbfgs_lincomb(int64_t n, float ca, const float *a, float cb, const float *b, int device, float *out) {
+    if (!a || !out) return fail(PLM_EINVAL, "NULL argument");
+    PLM_TRY(lbfgs_probe_length(n));
+    PLM_TRY(check_device(device));
+    LbfgsProbe P;
+    float *da, *db = nullptr, *dout;
+    PLM_TRY(P.upload(&da, a, (size_t)n));
+    if (b) PLM_TRY(P.upload(&db, b, (size_t)n));
+    PLM_TRY(P.nan_out(&dout, (size_t)n));
+    PLM_HIP(plm_launch_lincomb(dout, ca, da, cb, db, n, nullptr));
+    PLM_HIP(hipDeviceSynchronize());
+    PLM_TRY(P.download(out, dout, (size_t)n));
+    return PLM_OK;
+}
+
+int plm_ctx_precond_diagonal(plm_ctx_t *c, float *canonical_out) {
+    if (!c || !canonical_out) return fail(PLM_EINVAL, "NULL argument");
+    if (c->d.nshards != 1 || c->d.sharded) return fail(PLM_EINVAL, "the H0 diagonal is returned for single-shard contexts only");
+    if (c->h_fi.empty()) return fail(PLM_EINVAL, "the H0 diagonal needs single-site frequencies: run marginals first");
+    PLM_HIP(hipSetDevice(c->device));
+    PLM_TRY(ctx_build_dinv(c));
+    return get_vec(c, c->dinv, canonical_out);
 }
 
 int plm_ctx_time_kernels(plm_ctx_t *c, int32_t reps, float *out_ms) {

@@ -382,13 +382,10 @@ hipError_t plm_launch_multiaxpy(float *out, const PlmVecList &basis, const PlmCo
 // inverse Hessian diagonal of the independent-site model in the native layout; fv = [f | p(1-p)], 2*L*Q floats
 hipError_t plm_launch_precond(const PlmDims &d, const float *fv, float neff, float lambda_h, float lambda_j, float *dinv,
                               hipStream_t st);
-// s = x - xp ; y = g - gp in one pass
-hipError_t plm_launch_sy(float *s, float *y, const float *x, const float *xp, const float *g, const float *gp,
-                         int64_t n, hipStream_t st);
 // The vector work behind a trial point in ONE pass (round 6): the pair s = x - xp, y = g - gp is formed in registers, written
 // to its ring slot and used at once as the queries (s, y, g) of the Gram pass over `basis` -- the entries of `basis` that
 // ARE s_new / y_new / g are taken from the registers, the others read once -- together with g.dir, x.x and x.x over the first
-// nh entries (the fields).  Same accumulation per product as plm_launch_sy + plm_launch_multidot + three plm_launch_dots
+// nh entries (the fields).  Same accumulation per product as a pair pass + plm_launch_multidot + three plm_launch_dots
 // (same grid, same reduction tree: the same bits), 33 instead of 41 vector transfers per iteration.
 //   out_md[q * basis.n + k] as plm_launch_multidot (queries s_new, y_new, g), out_md[3 * basis.n] = s_new.s_new over the
 //   fields; out_ex[0..2] = g.dir, x.x, x.x (fields)

@@ -3644,23 +3644,6 @@ hipError_t plm_launch_multiaxpy_trial(float *out, const PlmVecList &basis, const
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_sy(float4 *__restrict__ s, float4 *__restrict__ y, const float4 *__restrict__ x,
-                                           const float4 *__restrict__ xp, const float4 *__restrict__ g,
-                                           const float4 *__restrict__ gp, int64_t n4) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        const float4 a = x[i], b = xp[i], c = g[i], e = gp[i];
-        s[i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
-        y[i] = make_float4(c.x - e.x, c.y - e.y, c.z - e.z, c.w - e.w);
-    }
-}
-hipError_t plm_launch_sy(float *s, float *y, const float *x, const float *xp, const float *g, const float *gp,
-                         int64_t n, hipStream_t st) {
-    if (n & 3) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_sy, dim3(2048), dim3(256), 0, st, (float4 *)s, (float4 *)y, (const float4 *)x,
-                       (const float4 *)xp, (const float4 *)g, (const float4 *)gp, n / 4);
-    return hipGetLastError();
-}
-
 // ---- the pair, the Gram pass and the scalar products of a trial point in one pass (plm_launch_sy_multidot) -------------
 #define SYD_OLD 10        // basis vectors read from memory per blockIdx.y: 2 (m - 1) at the default history m = 6
 struct PlmSyDot {

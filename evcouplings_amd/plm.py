@@ -807,6 +807,73 @@ def independent_fields(f_i, lambda_h, n_eff, device=0):
     return h, iters
 
 
+# ---- the L-BFGS vector kernels, test-facing (diagnostic: tests/test_gpu_lbfgs_vectors.py) ----
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _nan(shape, dtype):
+    return np.full(shape, np.nan, dtype)
+
+
+def lbfgs_gram(S, Y, x, xp, g, gp, direction, end, nst, nh, dinv=None, device=0):
+    """plm_lbfgs_gram: the pair and the Gram pass behind a trial point.  S, Y: (m, n) ring slots (slot `end` is
+    overwritten on the device only).  Returns (s_new, y_new, md [3 (2 nst + 2) + 1], ex [3])."""
+    S, Y, x, xp, g, gp, direction, dinv = (_f32(a) for a in (S, Y, x, xp, g, gp, direction, dinv))
+    m, n = S.shape
+    s_new, y_new = _nan(n, np.float32), _nan(n, np.float32)
+    md, ex = _nan(3 * (2 * nst + 2) + 1, np.float64), _nan(3, np.float64)
+    check(_lib.load().plm_lbfgs_gram(n, int(nh), m, int(end), int(nst), _ptr(S), _ptr(Y), _ptr(x), _ptr(xp), _ptr(g),
+                                     _ptr(gp), _ptr(direction), _ptr(dinv), device, _ptr(s_new), _ptr(y_new), _ptr(md),
+                                     _ptr(ex)))
+    return s_new, y_new, md, ex
+
+
+def lbfgs_direction(S, Y, g, cs, cy, cg, stored, end, dinv=None, xacc=None, stp0=0.0, device=0):
+    """plm_lbfgs_direction: the fused linear combination of the live pairs and g.  xacc given: the launch that also
+    writes the first trial point; returns (dir, trial), else dir alone."""
+    S, Y, g, dinv, xacc = (_f32(a) for a in (S, Y, g, dinv, xacc))
+    cs, cy = _f64(cs), _f64(cy)
+    m, n = S.shape
+    out = _nan(n, np.float32)
+    trial = None if xacc is None else _nan(n, np.float32)
+    check(_lib.load().plm_lbfgs_direction(n, m, int(stored), int(end), _ptr(S), _ptr(Y), _ptr(g), _ptr(cs), _ptr(cy),
+                                          float(cg), _ptr(dinv), _ptr(xacc), float(stp0), device, _ptr(out), _ptr(trial)))
+    return out if xacc is None else (out, trial)
+
+
+def lbfgs_multidot(V, q_index, b_index, dinv=None, wq=0, wb=0, device=0):
+    """plm_lbfgs_multidot: <V[q], V[b]> for every query / basis index, (len(q_index), len(b_index)) float64"""
+    V, dinv, q_index, b_index = _f32(V), _f32(dinv), _i32(q_index), _i32(b_index)
+    nv, n = V.shape
+    out = _nan((q_index.size, b_index.size), np.float64)
+    check(_lib.load().plm_lbfgs_multidot(n, nv, _ptr(V), q_index.size, _ptr(q_index), b_index.size, _ptr(b_index),
+                                         _ptr(dinv), int(wq), int(wb), device, _ptr(out)))
+    return out
+
+
+def lbfgs_dots(V, a_index, b_index, n=None, device=0):
+    """plm_lbfgs_dots: <V[a], V[b]> over the first n entries (default: all) for 1..4 index pairs"""
+    V, a_index, b_index = _f32(V), _i32(a_index), _i32(b_index)
+    nv, stride = V.shape
+    out = _nan(a_index.size, np.float64)
+    check(_lib.load().plm_lbfgs_dots(stride, nv, _ptr(V), a_index.size, _ptr(a_index), _ptr(b_index),
+                                     stride if n is None else int(n), device, _ptr(out)))
+    return out
+
+
+def lbfgs_lincomb(ca, a, cb=0.0, b=None, device=0):
+    """plm_lbfgs_lincomb: ca a + cb b in float32 (b None: ca a)"""
+    a, b = _f32(a), _f32(b)
+    out = _nan(a.size, np.float32)
+    check(_lib.load().plm_lbfgs_lincomb(a.size, float(ca), _ptr(a), float(cb), _ptr(b), device, _ptr(out)))
+    return out
+
+
 FLAG_IGNORE_GAPS = 2
 FLAG_SHARDED_STATE = 4
 FLAG_PRECOND = 8
@@ -1165,6 +1232,13 @@ class PlmContext:
                     continuations=res.continuations, final_skip=res.final_skip, want_rt=res.want_rt, cur=res.cur,
                     state_passes=res.state_passes, c_prev_next=res.c_prev_next, hist=np.array(res.hist[:]),
                     quiet=np.array(res.quiet[:], np.uint8), fields=fields)
+
+    def precond_diagonal(self):
+        """plm_ctx_precond_diagonal: the H0 diagonal of the preconditioned L-BFGS (diagnostic:
+        tests/test_gpu_lbfgs_vectors.py), canonical layout over all q states -- state 0 included when gaps are ignored"""
+        out = np.full(n_params(self.L, self.q), np.nan, np.float32)
+        check(self.lib.plm_ctx_precond_diagonal(self._h, _ptr(out)))
+        return out
 
     def time_field_positions(self, reps=5):
         """ms of one Hessian position and of the closing (residual-writing) position of the field solver's chain on this

@@ -774,6 +774,49 @@ typedef struct {
 int plm_ctx_field_solve(plm_ctx_t *ctx, double tol, int32_t vp_c_prev, int32_t invalidate, int32_t accurate,
                         plm_field_solve_t *result, double *fields, int64_t n_fields);
 
+/* -- L-BFGS vector kernels and H0 diagonal, test-facing (DIAGNOSTIC: tests/test_gpu_lbfgs_vectors.py; no product path
+ * calls these) ---------------------------------------------------------------------------------------------------------
+ * The plm_lbfgs_* entries run the launchers of the optimiser's vector kernels on HOST vectors, without an alignment or a
+ * context: upload, one launch, raw results back.  Before the launch the dot scratch (sized as a context sizes it) and
+ * every output buffer are filled with 0xFF bytes (NaN), so a partial sum or an output the kernels fail to write shows
+ * in the result.  Vector lengths are multiples of 4.  Invalid arguments: PLM_EINVAL, nothing is launched and no output
+ * is touched.
+ *
+ * plm_lbfgs_gram: the pass plm_ctx_optimize issues behind every trial point.  S, Y [nst][n]: ring slots 0 .. nst-1 of a
+ * history of m slots (nst = min(m, stored + 1), at most 20); the new pair s = x - xp, y = g - gp goes to slot `end`
+ * (end < nst; the slot's contents on entry are never read) and comes back in s_new, y_new [n].  The basis is the one
+ * the optimiser builds (same helper): S[0..nst), Y[0..nst), g, g -- nb = 2 nst + 2 vectors; products of the queries
+ * y_new and g with the Y's and the first g carry dinv [n] when it is given (NULL: plain products).
+ *   md [3 nb + 1]: md[q nb + k] = <query q, basis k> with q = (s_new, y_new, g); md[3 nb] = s_new.s_new over the first
+ *   nh entries;  ex [3] = g.dir, x.x, x.x over the first nh entries.  (nh: a multiple of 4 in 0..n.)
+ *
+ * plm_lbfgs_direction: dir = sum_j cs[j] s_j + dinv (.) (sum_j cy[j] y_j + cg g) over the `stored` live slots before
+ * `end` of S, Y [m][n] (basis order of the optimiser, same helper: live S newest to oldest, live Y likewise, g;
+ * coefficients rounded to f32); cs, cy [m] by physical slot as plm_lbfgs_coefficients returns them.  trial != NULL: the
+ * fused launch that also writes trial = xacc + stp0 * dir (xacc required); trial == NULL: the plain launch.
+ *
+ * plm_lbfgs_multidot: out[q nb + k] = <V[q_index[q]], V[b_index[k]]> for nq (1..4) queries and nb (1..42) basis vectors
+ * taken from V [nv][n]; bit q of wq and bit k of wb flag the products that carry dinv (both bits set, dinv given).
+ * plm_lbfgs_dots: out[p] = <V[a_index[p]], V[b_index[p]]> over the first n entries (n a multiple of 4 in 0..stride) of
+ * vectors V [nv][stride], 1..4 pairs.
+ * plm_lbfgs_lincomb: out = ca a + cb b, or ca a when b is NULL.
+ *
+ * plm_ctx_precond_diagonal: the inverse Hessian diagonal of the independent-site model at the start point (the H0 of
+ * PLM_FLAG_PRECOND), built by the code plm_ctx_optimize runs, in the canonical layout of plm_ctx_get_x.  Needs the
+ * context's marginals; single-shard contexts only (PLM_EINVAL otherwise). */
+int plm_lbfgs_gram(int64_t n, int64_t nh, int32_t m, int32_t end, int32_t nst, const float *S, const float *Y,
+                   const float *x, const float *xp, const float *g, const float *gp, const float *dir, const float *dinv,
+                   int device, float *s_new, float *y_new, double *md, double *ex);
+int plm_lbfgs_direction(int64_t n, int32_t m, int32_t stored, int32_t end, const float *S, const float *Y, const float *g,
+                        const double *cs, const double *cy, double cg, const float *dinv, const float *xacc, float stp0,
+                        int device, float *dir, float *trial);
+int plm_lbfgs_multidot(int64_t n, int32_t nv, const float *V, int32_t nq, const int32_t *q_index, int32_t nb,
+                       const int32_t *b_index, const float *dinv, uint32_t wq, uint64_t wb, int device, double *out);
+int plm_lbfgs_dots(int64_t stride, int32_t nv, const float *V, int32_t npairs, const int32_t *a_index,
+                   const int32_t *b_index, int64_t n, int device, double *out);
+int plm_lbfgs_lincomb(int64_t n, float ca, const float *a, float cb, const float *b, int device, float *out);
+int plm_ctx_precond_diagonal(plm_ctx_t *ctx, float *canonical_out);
+
 /* -- host arithmetic exposed for tests (no device) ------------------------------------------ */
 /* Two-loop recursion of L-BFGS in coefficient space over a ring of m history slots, of which the `stored` slots
  * before `end` (ring order, newest = end - 1) are live: direction p = sum_j cs[j] s_j + D^-1 (sum_j cy[j] y_j + cg g).
