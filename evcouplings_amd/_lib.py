@@ -148,6 +148,8 @@ class PlmAnnealResult(C.Structure):
 
 
 ANNEAL_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_void_p)
+PHI_CB = C.CFUNCTYPE(C.c_double, C.c_double, C.POINTER(C.c_double), C.c_void_p)
+LS_MAX_TRIALS = 20
 
 IDENT_DENOM = {"columns": 0, "both": 1, "shorter": 2}
 
@@ -275,6 +277,11 @@ SYMBOLS = [
     ("plm_rccl_probe_local", C.c_int, [C.c_int32, C.c_int, _P]),
     ("plm_lbfgs_coefficients", None, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("plm_linesearch_run", C.c_int, [PHI_CB, _P, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_double), _P]),
+    ("plm_lbfgs_admit", C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P,
+                                  _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
 _lib = None

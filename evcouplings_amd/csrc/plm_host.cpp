@@ -5,6 +5,7 @@
 #include "../../include/plm_hip.h"
 #include "plm_internal.h"
 #include "plm_host_util.h"
+#include "plm_lbfgs.h"
 
 #include <algorithm>
 #include <chrono>
@@ -213,48 +214,6 @@ int make_dims(const plm_problem_t &p, const PlmOptions &opt, PlmDims *out) {
 }
 
 }  // namespace
-
-// Two-loop recursion of L-BFGS (Nocedal 1980) in coefficient space: with the Gram matrix of {s_j, y_j, g} the direction
-//     p = sum_j cs[j] s_j + D^-1 (sum_j cy[j] y_j + cg g)      (D^-1 = I without preconditioning)
-// needs no pass over the vectors.  The history is a ring of m physical slots; the LIVE pairs are the `stored` slots before
-// `end` in ring order (newest = end - 1).  That is not always the physical range 0..stored-1: when a noise-dominated pair
-// is skipped on a full ring (plm_ctx_optimize), the dead slot is `end` -- wherever the ring stands.  Inputs and outputs
-// are indexed by PHYSICAL slot: SY[i*m+j] = s_i.y_j, YDY[i*m+j] = y_i.D^-1 y_j, Sg[i] = s_i.g, YDg[i] = y_i.D^-1 g,
-// gDg = g.D^-1 g; cs / cy get zeros in dead slots; *dg = g.p.  Exported for the host-side test (tests/test_host_layer.py).
-extern "C" void plm_lbfgs_coefficients(int m, int stored, int end, const double *SY, const double *YDY, const double *Sg,
-                                       const double *YDg, double gDg, double *cs, double *cy, double *cg_out,
-                                       double *dg_out) {
-    std::vector<double> alpha(m, 0.0);
-    std::vector<int> live(stored);                       // newest first
-    for (int i = 0; i < stored; i++) live[i] = (end + m - 1 - i) % m;
-    for (int j = 0; j < m; j++) cs[j] = cy[j] = 0.0;
-    double cg = -1.0;
-    // first loop (newest -> oldest): q = cg g + sum cy y lives in the plain space, only s_i.q is needed (cs is still zero)
-    for (int i = 0; i < stored; i++) {
-        const int j = live[i];
-        double v = cg * Sg[j];
-        for (int k : live) v += cy[k] * SY[j * m + k];
-        alpha[j] = v / SY[j * m + j];
-        cy[j] -= alpha[j];
-    }
-    if (stored > 0) {
-        const int newest = live[0];
-        const double gamma = SY[newest * m + newest] / YDY[newest * m + newest];
-        cg *= gamma;
-        for (int k : live) cy[k] *= gamma;
-    }
-    // second loop (oldest -> newest): r = sum cs s + D^-1 (cg g + sum cy y)
-    for (int i = stored - 1; i >= 0; i--) {
-        const int j = live[i];
-        double v = cg * YDg[j];
-        for (int k : live) v += cs[k] * SY[k * m + j] + cy[k] * YDY[j * m + k];
-        cs[j] += alpha[j] - v / SY[j * m + j];
-    }
-    double dg = cg * gDg;
-    for (int k : live) dg += cs[k] * Sg[k] + cy[k] * YDg[k];
-    *cg_out = cg;
-    *dg_out = dg;
-}
 
 struct plm_ctx {
     plm_problem_t prob;
@@ -740,84 +699,6 @@ int ctx_eval_vp_run(plm_ctx *c, double tol2, Fetch &&fetch, double *gh2_out) {
 int dots(plm_ctx *c, int npairs, const float *const *a, const float *const *b, int64_t n, int slot) {
     PLM_HIP(plm_launch_dots(npairs, a, b, n, c->dot_scratch, c->scal + slot, c->st));
     return PLM_OK;
-}
-
-// ---- More'-Thuente trial-step update (More' & Thuente 1994, sec. 4); scalar host code -------
-int mt_update(double *stx, double *fx, double *dx, double *sty, double *fy, double *dy, double *stp, double fp,
-              double dp, double tmin, double tmax, int *brackt) {
-    if (*brackt && (*stp <= std::min(*stx, *sty) || *stp >= std::max(*stx, *sty))) return -1;
-    if (*dx * (*stp - *stx) >= 0.0 || tmax < tmin) return -1;
-    const double sgnd = dp * (*dx / std::fabs(*dx));
-    double stpf, stpc, stpq, gamma, p, q, r, s, theta;
-    bool bound;
-    if (fp > *fx) {
-        bound = true;
-        theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-        s = std::max(std::fabs(theta), std::max(std::fabs(*dx), std::fabs(dp)));
-        gamma = s * std::sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-        if (*stp < *stx) gamma = -gamma;
-        p = (gamma - *dx) + theta;
-        q = ((gamma - *dx) + gamma) + dp;
-        r = p / q;
-        stpc = *stx + r * (*stp - *stx);
-        stpq = *stx + ((*dx / ((*fx - fp) / (*stp - *stx) + *dx)) / 2.0) * (*stp - *stx);
-        stpf = (std::fabs(stpc - *stx) < std::fabs(stpq - *stx)) ? stpc : stpc + (stpq - stpc) / 2.0;
-        *brackt = 1;
-    } else if (sgnd < 0.0) {
-        bound = false;
-        theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-        s = std::max(std::fabs(theta), std::max(std::fabs(*dx), std::fabs(dp)));
-        gamma = s * std::sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-        if (*stp > *stx) gamma = -gamma;
-        p = (gamma - dp) + theta;
-        q = ((gamma - dp) + gamma) + *dx;
-        r = p / q;
-        stpc = *stp + r * (*stx - *stp);
-        stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-        stpf = (std::fabs(stpc - *stp) > std::fabs(stpq - *stp)) ? stpc : stpq;
-        *brackt = 1;
-    } else if (std::fabs(dp) < std::fabs(*dx)) {
-        bound = true;
-        theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-        s = std::max(std::fabs(theta), std::max(std::fabs(*dx), std::fabs(dp)));
-        gamma = s * std::sqrt(std::max(0.0, (theta / s) * (theta / s) - (*dx / s) * (dp / s)));
-        if (*stp > *stx) gamma = -gamma;
-        p = (gamma - dp) + theta;
-        q = (gamma + (*dx - dp)) + gamma;
-        r = p / q;
-        if (r < 0.0 && gamma != 0.0) stpc = *stp + r * (*stx - *stp);
-        else stpc = (*stp > *stx) ? tmax : tmin;
-        stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-        if (*brackt) stpf = (std::fabs(*stp - stpc) < std::fabs(*stp - stpq)) ? stpc : stpq;
-        else stpf = (std::fabs(*stp - stpc) > std::fabs(*stp - stpq)) ? stpc : stpq;
-    } else {
-        bound = false;
-        if (*brackt) {
-            theta = 3.0 * (fp - *fy) / (*sty - *stp) + *dy + dp;
-            s = std::max(std::fabs(theta), std::max(std::fabs(*dy), std::fabs(dp)));
-            gamma = s * std::sqrt((theta / s) * (theta / s) - (*dy / s) * (dp / s));
-            if (*stp > *sty) gamma = -gamma;
-            p = (gamma - dp) + theta;
-            q = ((gamma - dp) + gamma) + *dy;
-            r = p / q;
-            stpf = *stp + r * (*sty - *stp);
-        } else {
-            stpf = (*stp > *stx) ? tmax : tmin;
-        }
-    }
-    if (fp > *fx) {
-        *sty = *stp; *fy = fp; *dy = dp;
-    } else {
-        if (sgnd < 0.0) { *sty = *stx; *fy = *fx; *dy = *dx; }
-        *stx = *stp; *fx = fp; *dx = dp;
-    }
-    stpf = std::max(tmin, std::min(tmax, stpf));
-    *stp = stpf;
-    if (*brackt && bound) {
-        const double lim = *stx + 0.66 * (*sty - *stx);
-        *stp = (*sty > *stx) ? std::min(lim, *stp) : std::max(lim, *stp);
-    }
-    return 0;
 }
 
 const char *status_text(int status) {
@@ -1401,9 +1282,9 @@ static void lbfgs_gram_basis(const float *S, const float *Y, const float *g, int
 static int lbfgs_direction_basis(const float *S, const float *Y, const float *g, int64_t n, int m, int stored, int end,
                                  const double *cs, const double *cy, double cg, PlmVecList *B, PlmCoefList *C) {
     B->n = 0;
-    for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B->v[B->n] = S + (size_t)j * n; C->c[B->n++] = (float)cs[j]; }
+    for (int i = 0; i < stored; i++) { const int j = lbfgs_live_slot(m, end, i); B->v[B->n] = S + (size_t)j * n; C->c[B->n++] = (float)cs[j]; }
     const int first_weighted = B->n;
-    for (int i = 0; i < stored; i++) { const int j = (end + m - 1 - i) % m; B->v[B->n] = Y + (size_t)j * n; C->c[B->n++] = (float)cy[j]; }
+    for (int i = 0; i < stored; i++) { const int j = lbfgs_live_slot(m, end, i); B->v[B->n] = Y + (size_t)j * n; C->c[B->n++] = (float)cy[j]; }
     B->v[B->n] = g;
     C->c[B->n++] = (float)cg;
     return first_weighted;
@@ -1426,21 +1307,6 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     const int64_t n = d.n_local;
     const int m = std::min(20, c->prob.lbfgs_m > 0 ? c->prob.lbfgs_m : 6);
     const int max_iter = c->prob.max_iter;
-    const int max_ls = 20;
-    const double ftol = 1e-4, gtol = 0.9, xtol = 1e-7, stpmin = 1e-20, stpmax = 1e20;
-    // f is an f64 sum of ~N L f32 terms: its rounding noise is ~1e-10 |f| (measured: 2e-3 at f = 2.8e7, N = 100 000),
-    // while the gradient -- exact integer sums of 24-bit residuals since round 3 -- is good to a few 1e-4 of |x|.  Near
-    // the optimum of a large problem the decrease of an iteration (stp |g.d| / 2) falls below that noise before the stop
-    // rule is met; a More'-Thuente search fed with such values interpolates on noise (seen at config 3: trials that
-    // wander between two step lengths until the bracket collapses, accepted steps that raise f).  Two devices:
-    //  * approximate Wolfe (Hager & Zhang 2005), as in the f32 oracle build: a trial whose f did not rise beyond
-    //    epsf |f0| passes the sufficient-decrease test;
-    //  * where |f(trial) - f(0)| is inside flat_rel |f(0)| AND the evaluated value contradicts what the derivatives
-    //    imply, f(0) + stp (g0.d + g.d) / 2 (trapezoid: exact for a quadratic), by more than half of that implied change,
-    //    the search works with the implied value -- then the sufficient-decrease test is H&Z's derivative form
-    //    g.d <= (2 ftol - 1) g0.d and the cubic steps see consistent data.  Small problems never get there (their f is
-    //    good to ~1e-10 |f| too, and that is far below their decreases).
-    const double epsf = 1e-6, flat_rel = 4e-9;
     PLM_TRY(ctx_alloc_lbfgs(c, m));
     float *S = c->hist, *Y = c->hist + (size_t)m * n;
     // H0 = gamma * D^-1 with D the Hessian diagonal of the independent-site model at the start point (closed form
@@ -1449,11 +1315,8 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     const bool precond = (c->prob.flags & PLM_FLAG_PRECOND) && !c->h_fi.empty();
     if (precond) PLM_TRY(ctx_build_dinv(c));
     const float *dinv = precond ? c->dinv : nullptr;
-    // Gram matrix pieces, indexed by history slot: SY[i][j] = s_i.y_j, YDY[i][j] = y_i.D^-1 y_j, Sg = s_i.g,
-    // YDg = y_i.D^-1 g, gDg = g.D^-1 g, gg = g.g (stop rule)
-    std::vector<double> SY(m * m, 0.0), YDY(m * m, 0.0), Sg(m, 0.0), YDg(m, 0.0);
-    double gg = 0, gDg = 0, xx = 0, hh = 0;
-    std::vector<double> cs(m), cy(m);
+    LbfgsHistory hist(m);      // the ring of pairs and the Gram matrix of {s_j, y_j, g} (plm_lbfgs.h)
+    double xx = 0, hh = 0;
     c->n_evals = 0;
     // device scalar slots; in sharded-state mode each fetch is preceded by a sum over the shards of
     // exactly the slots that were just written ([FX..DG] after an evaluation, [XX..MD+..] after the pass)
@@ -1466,16 +1329,13 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
         return PLM_OK;
     };
     // trial != nullptr: the launch also writes the first trial point of the line search, trial = xacc + stp0 * p
-    auto direction = [&](int stored, int end, double *dginit, const float *xacc, float stp0, float *trial) -> int {
-        // p = sum cs[j] s_j + D^-1 (sum cy[j] y_j + cg g): two-loop recursion in coefficient space over the LIVE pairs,
-        // the `stored` ring slots before `end` (after a skipped pair on a full ring the dead slot is `end` itself, not
-        // the highest physical slot)
+    auto direction = [&](double *dginit, const float *xacc, float stp0, float *trial) -> int {
         double cg;
-        plm_lbfgs_coefficients(m, stored, end, SY.data(), YDY.data(), Sg.data(), YDg.data(), gDg, cs.data(), cy.data(), &cg,
-                               dginit);
+        hist.coefficients(&cg, dginit);
         PlmVecList B;
         PlmCoefList C;
-        const int first_weighted = lbfgs_direction_basis(S, Y, c->g, n, m, stored, end, cs.data(), cy.data(), cg, &B, &C);
+        const int first_weighted =
+            lbfgs_direction_basis(S, Y, c->g, n, m, hist.stored, hist.end, hist.cs.data(), hist.cy.data(), cg, &B, &C);
         if (trial) PLM_HIP(plm_launch_multiaxpy_trial(c->dir, B, C, n, dinv, first_weighted, xacc, stp0, trial, c->st));
         else PLM_HIP(plm_launch_multiaxpy(c->dir, B, C, n, dinv, first_weighted, c->st));
         return PLM_OK;
@@ -1509,7 +1369,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     const double vp_rel = c->opt.vp_rel;
     c->vp_floor2 = ctx_vp_floor2(c);
     auto vp_tol2 = [&](double xnorm2) {
-        const double t = std::max(0.1 * eps * std::max(1.0, std::sqrt(xnorm2)), vp_rel * std::sqrt(gg));
+        const double t = std::max(0.1 * eps * std::max(1.0, std::sqrt(xnorm2)), vp_rel * std::sqrt(hist.gg));
         return t * t;
     };
     // Forward-GEMM mode.  The plain instantiation's f32 accumulation leaves an error of ~3e-11 N L |x| in the gradient
@@ -1544,8 +1404,8 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             if (!have) PLM_TRY(ctx_eval_enqueue(c));
             PLM_TRY(fetch());
         }
-        gDg = c->h_scal[SL_MD];
-        gg = c->h_scal[SL_MD + 1];
+        hist.gDg = c->h_scal[SL_MD];
+        hist.gg = c->h_scal[SL_MD + 1];
         xx = c->h_scal[SL_XX];
         hh = c->h_scal[SL_HH];
         return PLM_OK;
@@ -1555,7 +1415,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     double fx = resume ? c->last_fx : c->h_scal[SL_FX], nll = resume ? c->last_nll : c->h_scal[SL_NLL];
     c->eval_valid = false;
     if (!std::isfinite(fx)) return fail(PLM_ENUMERIC, "objective is not finite at the start point");
-    if (!c->fwd_accurate && want_accurate(std::sqrt(gg + gh2) / std::max(1.0, std::sqrt(xx)))) {
+    if (!c->fwd_accurate && want_accurate(std::sqrt(hist.gg + gh2) / std::max(1.0, std::sqrt(xx)))) {
         ctx_set_accurate(c, true);   // a start point this close to the optimum: its gradient decides the stop rule
         PLM_TRY(start_eval(false));
         fx = c->h_scal[SL_FX];
@@ -1583,12 +1443,8 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     double eps_eff = eps;      // target of the reduced gradient: the stop rule minus what the f32 rounding of the fields costs
     double rounding_note = 0;  // > 0: the rule was met on the f64-field point only; what rounding the fields to f32 adds
     int n_cert = 0;
-    int k = 0, end = 0, stored = 0, status = PLM_STATUS_CONVERGED, ls_reason = 0, restarts = 0;
-    // The next pair is (x - anchor, g - g(anchor)).  The anchor is the previous accepted point (xp, gp) -- unless the
-    // pair(s) since were skipped as noise (below): then it stays where the last STORED pair ended, in its own buffers,
-    // so that the difference is taken over a longer baseline, where H s outgrows the evaluation error again.
-    bool anchored = false;
-    double last_cond = std::sqrt(gg + gh2) / std::max(1.0, std::sqrt(xx));   // |g|/max(1,|x|) at the last accepted point
+    int k = 0, status = PLM_STATUS_CONVERGED, ls_reason = 0, restarts = 0;
+    double last_cond = std::sqrt(hist.gg + gh2) / std::max(1.0, std::sqrt(xx));   // |g|/max(1,|x|) at the last accepted point
     // (a resumed fit as well -- its previous run certified the point for ITS epsilon -- when the potentials of the
     // point are still there)
     if (last_cond <= eps && vp && (!resume || c->hj_at_x)) {   // a start point that meets the rule must meet it as it ships, too
@@ -1601,23 +1457,23 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     if (last_cond > eps) {
         // first step: unit displacement along the plain gradient; the D^-1-scaled direction is Newton-like for the
         // diagonal part of the Hessian, so it starts from min(1, that)
-        auto first_step = [&]() { return precond ? std::min(1.0, 1.0 / std::sqrt(gDg)) : 1.0 / std::sqrt(gg); };
+        auto first_step = [&]() { return precond ? std::min(1.0, 1.0 / std::sqrt(hist.gDg)) : 1.0 / std::sqrt(hist.gg); };
         double step = first_step();
         for (k = 1;; k++) {
             double dginit;
             // the direction and, in the same pass, the first trial point x + stp0 p -- written where the trial points are
             // built after the swap below (today's xp: the point before the accepted one, not needed any more unless it is
             // still the anchor of the next pair, which lives in its own buffers then)
-            const float stp0 = (float)std::max(stpmin, std::min(stpmax, step));
-            PLM_TRY(direction(stored, end, &dginit, c->x, stp0, c->xp));
+            const float stp0 = (float)std::max(MtSearch::stpmin, std::min(MtSearch::stpmax, step));
+            PLM_TRY(direction(&dginit, c->x, stp0, c->xp));
             if (!(dginit < 0)) { status = PLM_STATUS_LINESEARCH; ls_reason = 10; k--; break; }
             // the accepted point moves to (xp, gp); trial points are built in (x, g)
             std::swap(c->x, c->xp);
             std::swap(c->g, c->gp);
-            const double finit = fx, nllinit = nll, dgtest = ftol * dginit;
+            const double finit = fx, nllinit = nll;
             // the new pair goes into slot `end`; queries and basis of the Gram pass (rows for s, y, g)
-            float *s_new = S + (size_t)end * n, *y_new = Y + (size_t)end * n;
-            const int nst = std::min(m, stored + 1);
+            float *s_new = S + (size_t)hist.end * n, *y_new = Y + (size_t)hist.end * n;
+            const int nst = hist.nst();
             PlmVecList B;
             unsigned long long wb;                        // basis vectors that enter products in the H0 metric: Y, g
             unsigned wq;                                  // queries y_new and g
@@ -1635,7 +1491,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                 // synchronisation (and, sharded, one all-reduce) per trial brings back f, the directional
                 // derivative and everything the next direction needs.
                 // (round 6: pair, Gram rows, g.p, x.x and the fields' x.x in ONE pass over the vectors)
-                PLM_HIP(plm_launch_sy_multidot(s_new, y_new, c->x, anchored ? c->xa : c->xp, c->g, anchored ? c->ga : c->gp,
+                PLM_HIP(plm_launch_sy_multidot(s_new, y_new, c->x, hist.anchored ? c->xa : c->xp, c->g, hist.anchored ? c->ga : c->gp,
                                                c->dir, B, n, d.nh_pad_l, c->dot_scratch, c->scal + SL_MD, c->scal + SL_DG, dinv,
                                                wq, wb, c->st));
                 PLM_TRY(ctx_allreduce_scalars(c, SL_FX, SL_MD + 3 * B.n + 1 - SL_FX));
@@ -1646,76 +1502,20 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
               }
                 return PLM_OK;
             };
-            int brackt = 0, stage1 = 1, count = 0, uinfo = 0, lsrc = 1;
-            double width = stpmax - stpmin, prev_width = 2.0 * width;
-            double stx = 0, fxx = finit, dgx = dginit, sty = 0, fy = finit, dgy = dginit, stp = step, stmin, stmax;
-            double trace[64][3];
-            for (;;) {
-                if (brackt) { stmin = std::min(stx, sty); stmax = std::max(stx, sty); }
-                else { stmin = stx; stmax = stp + 4.0 * (stp - stx); }
-                stp = std::max(stpmin, std::min(stpmax, stp));
-                if ((brackt && (stp <= stmin || stmax <= stp || count >= max_ls - 1 || uinfo)) ||
-                    (brackt && stmax - stmin <= xtol * stmax))
-                    stp = stx;
-                if (!(count == 0 && (float)stp == stp0))      // the first trial point came with the direction
+            MtSearch ls;
+            ls.start(finit, dginit, step);
+            int lsrc;
+            do {
+                const double stp = ls.next();
+                if (!(ls.count == 0 && (float)stp == stp0))      // the first trial point came with the direction
                     PLM_HIP(plm_launch_lincomb(c->x, 1.f, c->xp, (float)stp, c->dir, n, c->st));
                 PLM_TRY(evaluate_trial());
                 double dg = c->h_scal[SL_DG];
                 fx = c->h_scal[SL_FX];
                 nll = c->h_scal[SL_NLL];
-                if (!std::isfinite(fx) || !std::isfinite(dg)) {
-                    // the trial left the region where the objective is representable: the interpolation formulas
-                    // of mt_update are meaningless on it (NaN steps).  Make the trial the far end of the bracket
-                    // with a finite stand-in value and bisect towards the best point found so far.
-                    if (count < 64) { trace[count][0] = stp; trace[count][1] = INFINITY; trace[count][2] = 0; }
-                    if (++count >= max_ls) { lsrc = -5; break; }
-                    sty = stp;
-                    fy = fxx + std::fabs(fxx) + 1.0;
-                    dgy = std::fabs(dgx);
-                    brackt = 1;
-                    stp = stx + 0.5 * (stp - stx);
-                    width = std::fabs(sty - stx);
-                    prev_width = 2.0 * width;
-                    continue;
-                }
-                const double ftest1 = finit + stp * dgtest;
-                // the value the search works with: the evaluated one, or inside the noise band the derivative-implied one
-                const double f_implied = finit + 0.5 * stp * (dginit + dg);
-                const bool noisy = std::fabs(fx - finit) <= flat_rel * std::fabs(finit) &&
-                                   std::fabs(fx - f_implied) > 0.5 * std::fabs(f_implied - finit) + 1e-12 * std::fabs(finit);
-                const double fl = noisy ? f_implied : fx;
-                if (count < 64) { trace[count][0] = stp; trace[count][1] = fx - finit; trace[count][2] = dg; }
-                count++;
-                if (brackt && (stp <= stmin || stmax <= stp || uinfo)) { lsrc = -1; break; }
-                if (stp == stpmax && fl <= ftest1 && dg <= dgtest) { lsrc = -2; break; }
-                if (stp == stpmin && (ftest1 < fl || dgtest <= dg)) { lsrc = -3; break; }
-                if (brackt && stmax - stmin <= xtol * stmax) { lsrc = -4; break; }
-                if (count >= max_ls) { lsrc = -5; break; }
-                if ((fl <= ftest1 || (!noisy && fx <= finit + epsf * std::fabs(finit))) && std::fabs(dg) <= gtol * (-dginit)) {
-                    lsrc = 1;
-                    break;
-                }
-                if (stage1 && fl <= ftest1 && std::min(ftol, gtol) * dginit <= dg) stage1 = 0;
-                if (stage1 && ftest1 < fl && fl <= fxx) {
-                    double fm = fl - stp * dgtest, fxm = fxx - stx * dgtest, fym = fy - sty * dgtest;
-                    double dgm = dg - dgtest, dgxm = dgx - dgtest, dgym = dgy - dgtest;
-                    uinfo = mt_update(&stx, &fxm, &dgxm, &sty, &fym, &dgym, &stp, fm, dgm, stmin, stmax, &brackt);
-                    fxx = fxm + stx * dgtest; fy = fym + sty * dgtest;
-                    dgx = dgxm + dgtest; dgy = dgym + dgtest;
-                } else {
-                    uinfo = mt_update(&stx, &fxx, &dgx, &sty, &fy, &dgy, &stp, fl, dg, stmin, stmax, &brackt);
-                }
-                if (brackt) {
-                    if (0.66 * prev_width <= std::fabs(sty - stx)) stp = stx + 0.5 * (sty - stx);
-                    prev_width = width;
-                    width = std::fabs(sty - stx);
-                }
-            }
-            if (lsrc < 0 && c->opt.debug) {
-                fprintf(stderr, "[plm] line search failed at iteration %d: code %d, finit=%.6f dginit=%.6e step0=%.3e brackt=%d stx=%.6e sty=%.6e\n", k, -lsrc, finit, dginit, step, brackt, stx, sty);
-                for (int t = 0; t < count && t < 64; t++)
-                    fprintf(stderr, "[plm]   trial %d: stp=%.9e  f-f0=%.6e  dg=%.6e\n", t, trace[t][0], trace[t][1], trace[t][2]);
-            }
+                lsrc = ls.feed(fx, dg);
+            } while (lsrc == 0);
+            if (lsrc < 0 && c->opt.debug) ls.dump_failure(k, lsrc);
             if (lsrc < 0) {
                 // the last accepted point is still in (xp, gp): make it current again
                 std::swap(c->x, c->xp);
@@ -1723,13 +1523,11 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                 fx = finit;
                 nll = nllinit;
                 k--;
-                if (stored > 0 && restarts < 2) {
+                if (hist.stored > 0 && restarts < 2) {
                     // a stale quasi-Newton model is the usual reason near the f32 floor: drop the history
                     // and retry once from steepest descent before giving up
                     restarts++;
-                    stored = 0;
-                    end = 0;
-                    anchored = false;
+                    hist.reset();
                     step = first_step();
                     continue;
                 }
@@ -1739,12 +1537,12 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             }
             restarts = 0;
             if (c->opt.debug)
-                fprintf(stderr, "[plm] it %d: %d trial(s), step %.4e (first %.4e), f - f0 = %.6e, dg0 = %.4e, dg = %.4e%s\n", k, count, stp,
-                        trace[0][0], fx - finit, dginit, c->h_scal[SL_DG], c->fwd_accurate ? " [accurate]" : "");
-            step = stp;
+                fprintf(stderr, "[plm] it %d: %d trial(s), step %.4e (first %.4e), f - f0 = %.6e, dg0 = %.4e, dg = %.4e%s\n", k, ls.count, ls.stp,
+                        ls.trace[0][0], fx - finit, dginit, c->h_scal[SL_DG], c->fwd_accurate ? " [accurate]" : "");
+            step = ls.stp;
             // the pair of the accepted point already sits in slot `end` and its Gram rows in h_scal (see above)
             const double *md = c->h_scal + SL_MD;
-            const int nbv = B.n, e = end;
+            const int nbv = B.n;
             bool straddle = false;              // this step's pair would difference gradients of two arithmetics
             if (!c->fwd_accurate &&
                 want_accurate(std::sqrt(md[2 * nbv + 2 * nst + 1] + gh2_trial) / std::max(1.0, std::sqrt(c->h_scal[SL_XX])))) {
@@ -1755,19 +1553,11 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                 nll = c->h_scal[SL_NLL];
                 if (!std::isfinite(fx)) return fail(PLM_ENUMERIC, "objective is not finite after the switch of the forward GEMM");
             }
-            for (int j = 0; j < nst; j++) {
-                SY[e * m + j] = md[0 * nbv + nst + j];            // s_e . y_j
-                SY[j * m + e] = md[1 * nbv + j];                  // s_j . y_e
-                YDY[e * m + j] = YDY[j * m + e] = md[1 * nbv + nst + j];
-                Sg[j] = md[2 * nbv + j];
-                YDg[j] = md[2 * nbv + nst + j];
-            }
-            gDg = md[2 * nbv + 2 * nst];
-            gg = md[2 * nbv + 2 * nst + 1];
+            hist.absorb(md, nbv, nst);
             xx = c->h_scal[SL_XX];
             hh = c->h_scal[SL_HH];
             gh2 = gh2_trial;
-            const double xnorm = std::sqrt(xx), gnorm = std::sqrt(gg + gh2);
+            const double xnorm = std::sqrt(xx), gnorm = std::sqrt(hist.gg + gh2);
             last_cond = gnorm / std::max(1.0, xnorm);
             // a non-zero return cancels the fit (a pipeline's SIGTERM / SIGINT handler, evcouplings/utils/pipeline.py:476-545,
             // raised inside a Python callback): the point reached so far stays in the context
@@ -1791,52 +1581,15 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
                 eps_eff = std::min(0.9 * eps_eff, std::sqrt(eps * eps - r2));
             }
             if (max_iter > 0 && k >= max_iter) { status = PLM_STATUS_MAXITER; break; }
-            // Curvature pair of the accepted step (slot e).  s.y > 0 always holds under the Wolfe conditions -- for exact
-            // gradients.  Near the noise floor of the evaluation (config 3: error 1e-3 |x| at a stop rule of 1e-3) steps
-            // get so short that y = H s + (difference of two evaluation errors) is mostly the latter: s.y is then a tiny
-            // number of either sign, 1 / s.y blows the two-loop coefficients up (seen with PLM_DEBUG: directions whose
-            // g.d disagreed in sign with the value the coefficients imply, a unit step raising f by 8e14) and the fit
-            // ends in a line-search failure.  For a convex quadratic cos(s, H s) >= 2 sqrt(k) / (1 + k) with k the
-            // condition number (0.12 at the headline's 120 : 3.5e4; the field part of s lowers it to ~0.04), a pair of
-            // pure noise has cos ~ 1 / sqrt(P) = 2e-4: pairs below 1e-3 are not stored (the history keeps its other
-            // pairs; the slot is written again by the next iteration -- with a pair over the longer baseline from the
-            // anchor, see `anchored`).
-            // Variable projection: y has no field part (the reduced gradient's is zero), the curvature information of the pair
-            // lives in the couplings -- but s carries the CHANGE OF THE OPTIMAL FIELDS as well, which enters no product of the
-            // two-loop recursion and only lowers cos(s, y) (0.12 -> 0.04 at the headline; at N = 500 000 below the admission
-            // rule: every pair of the accurate phase was skipped and the history went stale, NOTES_r06.md).  The rule looks at
-            // the coupling part of s.
-            const double ss_full = md[0 * nbv + e], ss_h = vp ? std::min(ss_full, std::max(0.0, md[3 * nbv])) : 0.0;
-            const double sy = SY[e * m + e], ss = std::max(ss_full - ss_h, 1e-300), yy = md[1 * nbv + nst + e];
-            if (c->opt.debug)
-                fprintf(stderr, "[plm]        pair: s.y = %.4e, |s| = %.4e (couplings %.4e), |y| = %.4e, cos = %.3e; history %d pair(s)%s%s\n",
-                        sy, std::sqrt(ss_full), std::sqrt(ss), std::sqrt(yy), sy / std::sqrt(std::max(1e-300, ss * yy)), stored,
-                        anchored ? ", anchored" : "", straddle ? ", straddle" : "");
-            if (straddle) {
-                // y = g_accurate(x) - g_plain(previous x) carries the DIFFERENCE of the two evaluations' errors (~3e-11 N L
-                // |x|): not a curvature pair.  It is dropped (slot e, the oldest pair once the ring is full, goes with it);
-                // the next pair starts from this point, whose gradient is the accurate one.
-                stored = std::min(stored, m - 1);
-                anchored = false;
-            } else if (sy > 0 && sy * sy >= 1e-6 * ss * yy) {
-                stored = nst;
-                end = (end + 1) % m;
-                anchored = false;
-            } else if (sy > 0) {       // noise-dominated pair: skipped; slot e (the oldest pair once the ring is full) is gone
-                stored = std::min(stored, m - 1);
-                if (!anchored) {       // keep the point the pair started from: (xp, gp) is overwritten by the next swap
-                    if (!c->xa) {
-                        PLM_TRY(plm_dalloc(&c->xa, (size_t)n));
-                        PLM_TRY(plm_dalloc(&c->ga, (size_t)n));
-                    }
-                    PLM_HIP(hipMemcpyAsync(c->xa, c->xp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-                    PLM_HIP(hipMemcpyAsync(c->ga, c->gp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-                    anchored = true;
+            // the pair of the accepted step: stored, dropped as a straddle, skipped as noise, or the history restarted
+            if (hist.admit(md, nbv, nst, vp, straddle, c->opt.debug).copy_anchor) {
+                // keep the point the pair started from: (xp, gp) is overwritten by the next swap
+                if (!c->xa) {
+                    PLM_TRY(plm_dalloc(&c->xa, (size_t)n));
+                    PLM_TRY(plm_dalloc(&c->ga, (size_t)n));
                 }
-            } else {                   // slot e now holds a rejected pair: restart the history
-                stored = 0;
-                end = 0;
-                anchored = false;
+                PLM_HIP(hipMemcpyAsync(c->xa, c->xp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
+                PLM_HIP(hipMemcpyAsync(c->ga, c->gp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
             }
             step = 1.0;
             // (Rounds 4-5 kept a stagnation watch here -- no new best |g|/|x| for 12 iterations next to the stop rule ->

@@ -874,6 +874,44 @@ def lbfgs_lincomb(ca, a, cb=0.0, b=None, device=0):
     return out
 
 
+# ---- line search and pair history of the optimiser, host only (diagnostic: tests/test_linesearch_host.py) ----
+def linesearch_run(phi, finit, dginit, step0):
+    """plm_linesearch_run: the optimiser's More'-Thuente search on phi(stp) -> (f, f').  Returns (code, n_trials, stp,
+    trace (n_trials, 3) of (stp, f - f0, f')); no device is touched."""
+    def cfunc(stp, dphi, user):
+        f, dphi[0] = phi(stp)
+        return f
+    code, count, stp = C.c_int32(0), C.c_int32(0), C.c_double(0)
+    trace = _nan((_lib.LS_MAX_TRIALS, 3), np.float64)
+    check(_lib.load().plm_linesearch_run(_lib.PHI_CB(cfunc), None, float(finit), float(dginit), float(step0),
+                                         C.byref(code), C.byref(count), C.byref(stp), _ptr(trace)))
+    return code.value, count.value, stp.value, trace[:count.value]
+
+
+ADMIT_STORED, ADMIT_STRADDLE, ADMIT_SKIPPED, ADMIT_RESTARTED = 0, 1, 2, 3
+
+
+def lbfgs_admit(state, md, vp=False, straddle=False):
+    """plm_lbfgs_admit: the Gram rows of an accepted step's pair go into the history, then the pair is admitted or
+    not.  state: dict(m, stored, end, anchored, SY, YDY (m, m), Sg, YDg (m), gDg, gg); md: the Gram pass's results
+    [3 (2 nst + 2) + 1].  Returns (new state, outcome, copy_anchor); no device is touched."""
+    m = int(state["m"])
+    SY, YDY, Sg, YDg = (_f64(state[k]).copy() for k in ("SY", "YDY", "Sg", "YDg"))
+    md = _f64(md)
+    stored, end, anchored = (C.c_int32(int(state[k])) for k in ("stored", "end", "anchored"))
+    gDg, gg = C.c_double(state["gDg"]), C.c_double(state["gg"])
+    outcome, copy_anchor = C.c_int32(-1), C.c_int32(-1)
+    nst = min(m, stored.value + 1)
+    if SY.shape != (m, m) or YDY.shape != (m, m) or Sg.shape != (m,) or YDg.shape != (m,) or md.size != 3 * (2 * nst + 2) + 1:
+        raise ValueError("history arrays or md of the wrong shape")
+    check(_lib.load().plm_lbfgs_admit(m, C.byref(stored), C.byref(end), C.byref(anchored), _ptr(SY), _ptr(YDY), _ptr(Sg),
+                                      _ptr(YDg), C.byref(gDg), C.byref(gg), _ptr(md), 2 * nst + 2, nst, int(bool(vp)),
+                                      int(bool(straddle)), C.byref(outcome), C.byref(copy_anchor)))
+    new = dict(m=m, stored=stored.value, end=end.value, anchored=bool(anchored.value), SY=SY, YDY=YDY, Sg=Sg, YDg=YDg,
+               gDg=gDg.value, gg=gg.value)
+    return new, outcome.value, bool(copy_anchor.value)
+
+
 FLAG_IGNORE_GAPS = 2
 FLAG_SHARDED_STATE = 4
 FLAG_PRECOND = 8

@@ -825,6 +825,33 @@ int plm_ctx_precond_diagonal(plm_ctx_t *ctx, float *canonical_out);
 void plm_lbfgs_coefficients(int m, int stored, int end, const double *SY, const double *YDY, const double *Sg,
                             const double *YDg, double gDg, double *cs, double *cy, double *cg, double *dg);
 
+/* DIAGNOSTIC (tests/test_linesearch_host.py; no product path calls these, neither initialises a device).
+ *
+ * plm_linesearch_run: the More'-Thuente line search of plm_ctx_optimize -- same code, same constants (ftol 1e-4,
+ * gtol 0.9, xtol 1e-7, steps in 1e-20 .. 1e20, at most PLM_LS_MAX_TRIALS trials, approximate-Wolfe allowance 1e-6 |f0|,
+ * noise band 4e-9 |f0|) -- on a function of one variable: phi returns f(stp) and writes f'(stp) to *dphi.  It starts
+ * from finit = f(0), dginit = f'(0) and the first trial step step0 > 0.
+ *   *code: 1 accepted; -1 the step left the bracket or made no progress, -2 / -3 the largest / smallest step, -4 the
+ *   bracket fell below xtol, -5 too many trials; -10 dginit is not negative (no trial is made).  *n_trials: trials
+ *   made.  *stp: the accepted step -- 0 after a failure: the optimiser returns to the point it started from.
+ *   trace [PLM_LS_MAX_TRIALS][3]: per trial (stp, f - f0, f'); f - f0 is +inf for a trial whose f or f' was not finite.
+ *
+ * plm_lbfgs_admit: what plm_ctx_optimize does with the curvature pair of an accepted step.  The history is a ring of
+ * m (1..20) slots with *stored live pairs before slot *end and the Gram pieces SY, YDY [m][m], Sg, YDg [m], *gDg, *gg
+ * laid out as for plm_lbfgs_coefficients.  md [3 nbv + 1] is the result of the Gram pass behind the accepted point as
+ * plm_lbfgs_gram returns it (nst = min(m, stored + 1), nbv = 2 nst + 2, the new pair in slot *end).  First the pair's
+ * rows are copied into the Gram pieces, then the pair is admitted or not (vp: the rule looks at the coupling part of s,
+ * md[3 nbv] being the fields' share of s.s; straddle: the pair differences gradients of two arithmetics).  Everything
+ * is updated in place.  *outcome: 0 stored, 1 dropped as a straddle, 2 skipped as noise, 3 history restarted;
+ * *copy_anchor: 1 when the optimiser would now copy the pair's starting point into its anchor buffers. */
+#define PLM_LS_MAX_TRIALS 20
+typedef double (*plm_phi_cb)(double stp, double *dphi, void *user);
+int plm_linesearch_run(plm_phi_cb phi, void *user, double finit, double dginit, double step0, int32_t *code,
+                       int32_t *n_trials, double *stp, double *trace);
+int plm_lbfgs_admit(int32_t m, int32_t *stored, int32_t *end, int32_t *anchored, double *SY, double *YDY, double *Sg,
+                    double *YDg, double *gDg, double *gg, const double *md, int32_t nbv, int32_t nst, int32_t vp,
+                    int32_t straddle, int32_t *outcome, int32_t *copy_anchor);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
