@@ -189,6 +189,27 @@ class PlmFieldSolve(C.Structure):
     ]
 
 
+MUT_OK, MUT_ETOOMANY, MUT_EPOSITION, MUT_ESTATE, MUT_EREPEAT = 0, 1, 2, 3, 4
+SCAN_MAX_SITES, SCAN_MAX_EDGES = 8, 1024
+
+
+class PlmScanOpts(C.Structure):
+    _fields_ = [
+        ("n_scan_sites", C.c_int32), ("flags", C.c_int32),
+        ("sites", C.c_void_p), ("letter_offsets", C.c_void_p), ("letters", C.c_void_p),
+        ("first", C.c_int64), ("count", C.c_int64),
+        ("edges", C.c_void_p), ("n_edges", C.c_int32), ("use_threshold", C.c_int32),
+        ("threshold", C.c_double), ("capacity", C.c_int64),
+    ]
+
+
+class PlmScanResult(C.Structure):
+    _fields_ = [
+        ("energies", C.c_void_p), ("histogram", C.c_void_p), ("kept_index", C.c_void_p), ("kept_energies", C.c_void_p),
+        ("dh_min", C.c_double), ("dh_max", C.c_double), ("n_kept", C.c_int64), ("n_combinations", C.c_int64),
+    ]
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -282,6 +303,10 @@ SYMBOLS = [
     ("plm_lbfgs_admit", C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P,
                                   _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("plm_mutant_effects", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, _P, _P, _P,
+                                     _P]),
+    ("plm_mutant_scan", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(PlmScanOpts), C.c_int, _P,
+                                  C.POINTER(PlmScanResult)]),
 ]
 
 _lib = None

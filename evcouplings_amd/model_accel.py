@@ -20,6 +20,10 @@ Boltzmann-machine loop (`plm_bm_fit`, section 9.7), so that its samples reproduc
 `log_probabilities(model, sequences, log_z)` turns statistical energies into log-probabilities with it.
 `optimize_sequences(model, n)` searches a model for its highest-scoring sequences by simulated annealing and greedy
 ascent (`plm_anneal`, section 9.13), and `local_optima(model, sequences)` climbs from given sequences.
+`install(mutations=True)` also rebinds the mutate stage's `predict_mutation_table` (mutate/calculations.py:54-180, one
+`delta_hamiltonian` call per table row) to one `plm_mutant_effects` call per table (section 9.16): `parse_mutations`,
+`delta_hamiltonians`, `predict_mutation_table`; `scan_library(model, positions)` ranks every letter combination at a few
+positions (`plm_mutant_scan`).  Off by default.
 """
 from copy import deepcopy
 
@@ -28,6 +32,9 @@ import numpy as np
 _ORIGINAL = {}
 _ANALYSIS = {}                 # class -> {attribute name: the class's own attribute before install(analysis=True)}
 _ANALYSIS_NAMES = ("_calculate_ecs", "double_mut_mat", "to_independent_model")
+_MUTATE = {}                   # module -> its own predict_mutation_table before install(mutations=True)
+COMPONENT_TO_INDEX = {"full": 0, "couplings": 1, "fields": 2}
+_WILD_TYPE = ("wild", "wt", "")
 
 
 def _pairs_from_dense(J_ij):
@@ -423,6 +430,167 @@ def to_independent_model(self):
     return c0
 
 
+# ---- mutation tables and combinatorial libraries (DESIGN_NEXT_ROWS.md section 9.16) ------------------------------
+
+def _hashable(key):
+    if isinstance(key, (list, tuple, np.ndarray)):
+        return tuple(_hashable(k) for k in key)
+    return key.item() if isinstance(key, np.generic) else key
+
+
+def _model_maps(model):
+    """(index_map, alphabet_map) of a model: its own where it has them (CouplingsModel), else built from `index_list`
+    and `alphabet`."""
+    index_map = getattr(model, "index_map", None)
+    if index_map is None:
+        index_map = {_hashable(b): a for a, b in enumerate(model.index_list)}
+    alphabet_map = getattr(model, "alphabet_map", None)
+    if alphabet_map is None:
+        alphabet_map = {a: k for k, a in enumerate(np.asarray(list(model.alphabet)).astype("U1"))}
+    return index_map, alphabet_map
+
+
+def _target_states(model, alphabet_map):
+    mapped = getattr(model, "target_seq_mapped", None)
+    if mapped is None:
+        mapped = [alphabet_map[a] for a in model.target_seq]
+    return np.asarray(mapped).astype(np.int8)
+
+
+def extract_mutations(mutation_string, offset=0, sep=","):
+    """"K50R,I100V" -> [(50, "K", "R"), (100, "I", "V")]; "wild", "wt" and "" (any case) -> []: the reference's
+    function of that name (mutate/calculations.py:25-51), a ValueError for a position that is no integer included."""
+    if mutation_string.lower() in _WILD_TYPE:
+        return []
+    return [(int(x[1:-1]) + offset, x[0], x[-1]) for x in mutation_string.split(sep)]
+
+
+def parse_mutations(model, mutants, segments=None):
+    """
+    A table of mutants as the CSR arrays of `plm.mutant_effects`.  mutants: one entry per row, a string as
+    `extract_mutations` takes it or a list of (position, from, to) substitutions as `CouplingsModel.delta_hamiltonian`
+    takes it; segments: None, one segment identifier for every substitution, or one comma-separated string per row
+    (a substitution of position p in segment s addresses the model position (s, p); substitutions beyond the row's
+    segments are dropped, as the reference's zip does).  Positions go through `model.index_map`, letters through
+    `model.alphabet_map`.
+    Returns (offsets int64 [n + 1], positions int32, states int8, invalid bool [n]): `invalid` marks the rows the
+    reference turns into NaN (a position or letter the model does not have, a from-letter that is not the target's);
+    they are stored with no substitutions.
+    """
+    index_map, alphabet_map = _model_maps(model)
+    target = model.target_seq
+    per_row = segments is not None and not isinstance(segments, str)
+    if per_row:
+        segments = list(segments)
+    offsets, positions, states, invalid = [0], [], [], []
+    for r, m in enumerate(mutants):
+        subs = extract_mutations(m) if isinstance(m, str) else list(m)
+        if per_row:
+            subs = [((seg, pos), a, b) for seg, (pos, a, b) in zip(segments[r].split(","), subs)]
+        elif segments is not None:
+            subs = [((segments, pos), a, b) for pos, a, b in subs]
+        row_pos, row_st, bad = [], [], False
+        for pos, a_from, a_to in subs:
+            try:
+                i = index_map[_hashable(pos)]
+                row_st.append(alphabet_map[a_to])
+            except (KeyError, TypeError):
+                bad = True
+                break
+            if a_from != target[i]:
+                bad = True
+                break
+            row_pos.append(i)
+        if bad:
+            row_pos, row_st = [], []
+        positions.extend(row_pos)
+        states.extend(row_st)
+        offsets.append(len(positions))
+        invalid.append(bad)
+    return (np.asarray(offsets, np.int64), np.asarray(positions, np.int32), np.asarray(states, np.int8),
+            np.asarray(invalid, bool))
+
+
+def _effects(model, parsed, device=0):
+    """n x 3 (dH, dH_J, dH_h) of parsed rows; NaN where the row is invalid or the library refused it (a position named
+    twice, which the reference counts twice)."""
+    from evcouplings_amd import plm
+    offsets, positions, states, invalid = parsed
+    h_i = np.asarray(model.h_i)
+    _, alphabet_map = _model_maps(model)
+    out, status = plm.mutant_effects(_target_states(model, alphabet_map), h_i.shape[1], h_i,
+                                     _pairs_from_dense(np.asarray(model.J_ij)), offsets, positions, states, device=device)
+    out = np.array(out, dtype=np.float64)
+    out[invalid | (np.asarray(status) != 0)] = np.nan
+    return out
+
+
+def delta_hamiltonians(model, substitutions, device=0):
+    """`CouplingsModel.delta_hamiltonian` (model.py:672-712) for a list of substitution lists [(pos, from, to), ...] in one
+    GPU call: n x 3 float64 (dH, dH_J, dH_h), NaN rows where the reference raises ValueError."""
+    return _effects(model, parse_mutations(model, substitutions), device=device)
+
+
+def predict_mutation_table(model, table, output_column="prediction_epistatic", mutant_column="mutant", hamiltonian="full",
+                           segment=None, parsed=None):
+    """
+    Drop-in for the reference's `predict_mutation_table` (mutate/calculations.py:54-180): the same arguments, column and
+    segment handling, NaN rows and ValueErrors, with one `plm.mutant_effects` call for the whole table in place of one
+    `delta_hamiltonian` call per row.  parsed: the return value of `parse_mutations` for this table, to score it with
+    several models that share positions, alphabet and target (the epistatic and the independent one) after one parse.
+    """
+    if hamiltonian not in COMPONENT_TO_INDEX:
+        raise ValueError("Invalid selection for hamiltonian. Valid values are: " + ", ".join(COMPONENT_TO_INDEX))
+    if not getattr(model, "has_target_seq", True):
+        raise ValueError("CouplingsModel object does not have a target sequence (non-focus mode). "
+                         "Set target sequence, or rerun inference in focus mode.")
+    pred = table.copy()
+    if parsed is None:
+        parsed = parse_table(model, pred, mutant_column=mutant_column, segment=segment)
+    pred.loc[:, output_column] = _effects(model, parsed)[:, COMPONENT_TO_INDEX[hamiltonian]]
+    return pred
+
+
+def parse_table(model, table, mutant_column="mutant", segment=None):
+    """`parse_mutations` of a mutant table: the index or `mutant_column`, with the table's own `segment` column if it
+    has one without nulls, else the `segment` argument."""
+    mutations = table.index if mutant_column is None else table.loc[:, mutant_column]
+    if "segment" in table.columns and table.loc[:, "segment"].notnull().all():
+        segment = list(table.loc[:, "segment"])
+    return parse_mutations(model, list(mutations), segments=segment)
+
+
+def scan_library(model, positions, exclude="-", top=100, device=0):
+    """
+    The `top` best members of the combinatorial library that varies the given positions (the model's numbering) of the
+    target over every letter not in `exclude`, by exhaustive enumeration on the GPU (`plm.top_combinations`).  Returns a
+    DataFrame, best first (ties in library order): `index` (the member's number in `itertools.product` order), `letters`
+    (its letters at the positions, in the order given), `mutant` (its substitutions in the notation of the mutate stage,
+    "wild" for the target itself) and `dH`, `dH_J`, `dH_h` relative to the target.
+    """
+    import pandas as pd
+    from evcouplings_amd import plm
+    h_i = np.asarray(model.h_i)
+    L, q = h_i.shape
+    index_map, alphabet_map = _model_maps(model)
+    letters, code = _letters_and_code(model, q)
+    try:
+        sites = [index_map[_hashable(p)] for p in positions]
+    except KeyError as e:
+        raise ValueError("position %s is not in the model's index_list" % e)
+    allowed = _allowed_flags(exclude, code, q)
+    states = np.arange(q) if allowed is None else np.nonzero(allowed)[0]
+    lists = [states] * len(sites)
+    idx, en = plm.top_combinations(_target_states(model, alphabet_map), q, h_i, _pairs_from_dense(np.asarray(model.J_ij)),
+                                   sites, letters=lists, top=top, device=device)
+    chosen = letters[states[plm.scan_digits(idx, [len(states)] * len(sites))]].reshape(len(idx), len(sites))
+    target = np.asarray(list(model.target_seq)).astype("U1")
+    names = [",".join("%s%s%s" % (target[s], p if not isinstance(p, tuple) else p[-1], a)
+                      for s, p, a in zip(sites, positions, row) if a != target[s]) or "wild" for row in chosen]
+    return pd.DataFrame({"index": idx, "letters": ["".join(row) for row in chosen], "mutant": names,
+                         "dH": en[:, 0], "dH_J": en[:, 1], "dH_h": en[:, 2]})
+
+
 def _analysis_original(cls, name):
     for k in cls.__mro__:
         if k in _ANALYSIS and name in _ANALYSIS[k]:
@@ -430,12 +598,14 @@ def _analysis_original(cls, name):
     raise AttributeError("%s.%s: model_accel analysis drop-ins are not installed" % (cls.__name__, name))
 
 
-def install(model_module=None, reader=False, analysis=False):
+def install(model_module=None, reader=False, analysis=False, mutations=False):
     """
     Rebind, in evcouplings.couplings.model (or the module object given): the two Hamiltonian loops and,
     if the module has a CouplingsModel class and `reader` is true, its plmc_v2 reader; if `analysis` is true, the
     class's `_calculate_ecs`, `double_mut_mat` and `to_independent_model` (subclasses such as
-    MeanFieldCouplingsModel reach them through super() or inheritance).  `uninstall()` restores all of them.
+    MeanFieldCouplingsModel reach them through super() or inheritance); if `mutations` is true, `predict_mutation_table`
+    in evcouplings.mutate.calculations and in evcouplings.mutate.protocol, which imports it by name.  `uninstall()`
+    restores all of them.
     """
     if model_module is None:
         import evcouplings.couplings.model as model_module
@@ -453,6 +623,12 @@ def install(model_module=None, reader=False, analysis=False):
         cls._calculate_ecs = calculate_ecs
         cls.double_mut_mat = double_mut_mat
         cls.to_independent_model = to_independent_model
+    if mutations:
+        import evcouplings.mutate.calculations as calculations
+        import evcouplings.mutate.protocol as mutate_protocol
+        for mod in (calculations, mutate_protocol):
+            _MUTATE.setdefault(mod, mod.predict_mutation_table)
+            mod.predict_mutation_table = predict_mutation_table
     return model_module
 
 
@@ -469,3 +645,6 @@ def uninstall(model_module=None):
     if cls in _ANALYSIS:
         for name, attr in _ANALYSIS.pop(cls).items():
             setattr(cls, name, attr)
+    while _MUTATE:
+        mod, original = _MUTATE.popitem()
+        mod.predict_mutation_table = original

@@ -807,6 +807,178 @@ def independent_fields(f_i, lambda_h, n_eff, device=0):
     return h, iters
 
 
+# ---- mutation tables and combinatorial libraries (DESIGN_NEXT_ROWS.md section 9.16) ------------------------------
+MUTANT_STATUS = {0: "ok", 1: "more entries than sites", 2: "position outside the model", 3: "state outside the alphabet",
+                 4: "position named twice"}
+
+
+def _target_model(target, q, hi, jij):
+    hi, jij, L = _potts_model(hi, jij, q)
+    target = np.ascontiguousarray(np.asarray(target).ravel(), dtype=np.int8)
+    if target.shape != (L,):
+        raise ValueError("target must hold %d states" % L)
+    return target, L, _canonical(hi, jij, L, q)
+
+
+def mutant_effects(target, q, hi, jij, offsets, positions, states, device=0, tables=False):
+    """
+    Energy differences of variants of `target`, the arithmetic of the reference's `_delta_hamiltonian`
+    (couplings/model.py:112-176) for a whole table at once.  Variant v substitutes, at the 0-based sites
+    positions[offsets[v]:offsets[v+1]], the states states[offsets[v]:offsets[v+1]].  Returns (out, status): out is
+    n x 3 float64 (dH, dH_J, dH_h), status n uint8 (0, or a key of MUTANT_STATUS with NaN in the row: more entries than
+    sites, a position or state outside the model, a position named twice).  With tables=True a third value follows:
+    the L x q x 2 float64 single-mutant tables (S_J, S_h).
+    """
+    lib = _lib.load()
+    target, L, x = _target_model(target, q, hi, jij)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+    positions = np.ascontiguousarray(positions, dtype=np.int32).ravel()
+    states = np.ascontiguousarray(states, dtype=np.int8).ravel()
+    if offsets.size < 1 or positions.size != states.size:
+        raise ValueError("offsets must hold n + 1 entries, positions and states one entry per substitution")
+    n = offsets.size - 1
+    out, status = np.empty((n, 3)), np.empty(n, np.uint8)
+    tab = np.empty((L, q, 2)) if tables else None
+    check(lib.plm_mutant_effects(_ptr(x), L, q, _ptr(target), n, _ptr(offsets), positions.size, _ptr(positions),
+                                 _ptr(states), device, None, _ptr(out), _ptr(status), _ptr(tab)))
+    return (out, status, tab) if tables else (out, status)
+
+
+def _scan_letters(letters, k, q):
+    """(letter_offsets int32 [k + 1], letters int8) of per-site letter lists; None: every state at every site."""
+    if letters is None:
+        letters = [range(q)] * k
+    if len(letters) != k:
+        raise ValueError("letters must hold one list per site")
+    lists = [np.asarray(list(l), dtype=np.int8) for l in letters]
+    lo = np.zeros(k + 1, np.int32)
+    lo[1:] = np.cumsum([len(l) for l in lists])
+    return lo, np.ascontiguousarray(np.concatenate(lists) if k else np.zeros(0), dtype=np.int8)
+
+
+def scan_digits(index, sizes):
+    """The digits (one column per site, the last site fastest) of combination indices for per-site list sizes."""
+    index = np.asarray(index, dtype=np.int64)
+    digits = np.empty(index.shape + (len(sizes),), np.int64)
+    for s in range(len(sizes) - 1, -1, -1):
+        index, digits[..., s] = np.divmod(index, int(sizes[s]))
+    return digits
+
+
+def mutant_scan(target, q, hi, jij, sites, letters=None, first=0, count=None, energies=False, edges=None, threshold=None,
+                capacity=1 << 16, device=0):
+    """
+    dH of every combination of letters at up to 8 distinct `sites` (0-based) of `target`.  letters: one list of states
+    per site (None: all q states).  Combinations are numbered like `itertools.product(*letters)`, the last site
+    fastest; the call covers [first, first + count) (count None: to the end).  Returns a dict: `n_combinations`, `first`,
+    `count`, `dh_min`, `dh_max` (exact extremes over the range); with energies=True `energies` (count x 3:
+    dH, dH_J, dH_h); with edges (ascending, at most 1024) `histogram` (uint64, len(edges) + 1: bin = number of edges
+    <= dH, i.e. `np.searchsorted(edges, dH, side="right")`); with threshold `n_kept` (how many have dH >= threshold) and,
+    unless n_kept > capacity (then `kept_index` is None: call again with the room), `kept_index` (ascending) and
+    `kept_energies`.
+    """
+    lib = _lib.load()
+    target, L, x = _target_model(target, q, hi, jij)
+    sites = np.ascontiguousarray(np.asarray(sites).ravel(), dtype=np.int32)
+    k = sites.size
+    lo, let = _scan_letters(letters, k, q)
+    total = 1
+    for s in range(k):
+        total *= int(lo[s + 1] - lo[s])
+    first = int(first)
+    count = max(total - first, 0) if count is None else int(count)
+    capacity = int(capacity) if threshold is not None else 0
+    en = np.empty((count, 3)) if energies else None
+    ed = hist = None
+    if edges is not None:
+        ed = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        n_edges = ed.size
+        ed = ed if n_edges else np.zeros(1)              # no edge at all: one bin; the library still wants a pointer
+        hist = np.zeros(n_edges + 1, np.uint64)
+    kidx = np.empty(capacity, np.int64) if capacity > 0 else None
+    ken = np.empty((capacity, 3)) if capacity > 0 else None
+    opts = _lib.PlmScanOpts(n_scan_sites=k, flags=0, sites=sites.ctypes.data,
+                            letter_offsets=lo.ctypes.data, letters=let.ctypes.data, first=first, count=count,
+                            edges=None if ed is None else ed.ctypes.data, n_edges=0 if ed is None else n_edges,
+                            use_threshold=int(threshold is not None), threshold=0.0 if threshold is None else float(threshold),
+                            capacity=capacity)
+    res = _lib.PlmScanResult()
+    for name, arr in (("energies", en), ("histogram", hist), ("kept_index", kidx), ("kept_energies", ken)):
+        if arr is not None:
+            setattr(res, name, arr.ctypes.data)
+    check(lib.plm_mutant_scan(_ptr(x), L, q, _ptr(target), C.byref(opts), device, None, C.byref(res)))
+    out = dict(n_combinations=int(res.n_combinations), first=first, count=count, dh_min=float(res.dh_min),
+               dh_max=float(res.dh_max))
+    if energies:
+        out["energies"] = en
+    if hist is not None:
+        out["histogram"] = hist
+    if threshold is not None:
+        n_kept = int(res.n_kept)
+        fits = n_kept <= capacity
+        out.update(n_kept=n_kept, kept_index=kidx[:n_kept].copy() if fits and n_kept else (np.zeros(0, np.int64) if fits else None),
+                   kept_energies=ken[:n_kept].copy() if fits and n_kept else (np.zeros((0, 3)) if fits else None))
+    return out
+
+
+def top_combinations(target, q, hi, jij, sites, letters=None, top=100, device=0, max_keep=None, chunk=1 << 24):
+    """
+    The `top` combinations of largest dH among all letter combinations at `sites` (as for `mutant_scan`), ordered by
+    (-dH, index): (index int64 [n], energies float64 [n, 3]), n = min(top, number of combinations).  One pass for the
+    extremes, then histograms over 1024 edges that narrow onto the bin holding the top-th value until a threshold keeps
+    at most max_keep combinations (default max(4 top, 2^20)), then one compacting pass whose buffer holds exactly what
+    the histogram counted.  Where values tie so densely that no threshold separates that few (the bin cannot be split
+    further), the library is walked in ranges of `chunk` combinations and the best are merged range by range.
+    """
+    top = int(top)
+    if top < 1:
+        raise ValueError("top must be >= 1")
+    kw = dict(letters=letters, device=device)
+    ext = mutant_scan(target, q, hi, jij, sites, **kw)
+    total = ext["n_combinations"]
+    top = min(top, total)
+    max_keep = max(4 * top, 1 << 20) if max_keep is None else max(int(max_keep), top)
+
+    def best(idx, en):
+        order = np.lexsort((idx, -en[:, 0]))[:top]
+        return idx[order], en[order]
+
+    def compact(thr, expect, first=0, count=None):
+        res = mutant_scan(target, q, hi, jij, sites, first=first, count=count, threshold=thr, capacity=max(expect, 1), **kw)
+        if res["kept_index"] is None:            # more than was counted: take what it reports, never the overflowed buffer
+            res = mutant_scan(target, q, hi, jij, sites, first=first, count=count, threshold=thr, capacity=res["n_kept"], **kw)
+        return res["kept_index"], res["kept_energies"]
+
+    lo, hi_ = ext["dh_min"], ext["dh_max"]
+    thr, n_kept = -np.inf, total
+    while n_kept > max_keep:
+        edges = np.linspace(lo, hi_, _lib.SCAN_MAX_EDGES)
+        edges[0], edges[-1] = lo, hi_
+        edges = np.maximum.accumulate(np.clip(edges, lo, hi_))
+        counts = mutant_scan(target, q, hi, jij, sites, edges=edges, **kw)["histogram"].astype(np.int64)
+        tail = counts[::-1].cumsum()[::-1]           # tail[b]: combinations in bin b or above, i.e. with dH >= edges[b - 1]
+        b = int(np.nonzero(tail >= top)[0].max())
+        if b == 0:                                   # cannot happen while lo is a lower bound of the top values
+            break
+        thr, n_kept = float(edges[b - 1]), int(tail[b])
+        if n_kept <= max_keep:
+            break
+        if b == edges.size:                          # that many sit at the maximum itself
+            break
+        upper = float(edges[b])
+        if not np.nextafter(thr, np.inf) < upper or (thr == lo and upper == hi_):
+            break                                    # the bin is one value wide, or did not narrow: ties
+        lo, hi_ = thr, upper
+    if n_kept <= max_keep:
+        return best(*compact(thr, n_kept))
+    idx, en = np.zeros(0, np.int64), np.zeros((0, 3))
+    for first in range(0, total, int(chunk)):
+        count = min(int(chunk), total - first)
+        ci, ce = compact(thr, min(count, max_keep), first, count)
+        idx, en = best(np.concatenate([idx, ci]), np.concatenate([en, ce]))
+    return idx, en
+
+
 # ---- the L-BFGS vector kernels, test-facing (diagnostic: tests/test_gpu_lbfgs_vectors.py) ----
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)

@@ -97,12 +97,13 @@ def unregister_protocols():
         cp.PROTOCOLS.pop(name, None)
 
 
-def install_all(analysis=False):
+def install_all(analysis=False, mutations=False):
     """run_plmc + the N2 / N3 / N4 drop-ins (model energies, alignment statistics, mean-field DCA); with `analysis`
-    also CouplingsModel's EC scores, double-mutant matrix and independent model (model_accel.install(analysis=True))."""
+    also CouplingsModel's EC scores, double-mutant matrix and independent model (model_accel.install(analysis=True));
+    with `mutations` also the mutate stage's predict_mutation_table (model_accel.install(mutations=True))."""
     from evcouplings_amd import alignment_accel, mean_field, model_accel
     install()
-    model_accel.install(analysis=analysis)
+    model_accel.install(analysis=analysis, mutations=mutations)
     mean_field.install()
     alignment_accel.install()
 

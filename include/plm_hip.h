@@ -852,6 +852,79 @@ int plm_lbfgs_admit(int32_t m, int32_t *stored, int32_t *end, int32_t *anchored,
                     double *YDg, double *gDg, double *gg, const double *md, int32_t nbv, int32_t nst, int32_t vp,
                     int32_t straddle, int32_t *outcome, int32_t *copy_anchor);
 
+/* ---- mutation tables and combinatorial libraries (DESIGN_NEXT_ROWS.md section 9.16) ------------------------------
+ * Energy differences relative to a target sequence t: the arithmetic of the reference's `_delta_hamiltonian`
+ * (couplings/model.py:112-176) that `predict_mutation_table` (mutate/calculations.py:54-180) calls once per table row,
+ * regrouped.  A variant changes sites i_1..i_M to letters a_1..a_M:
+ *   S_h[i,a]  = h_i(a) - h_i(t_i)             S_J[i,a] = sum_{j != i} ( J_ij(a, t_j) - J_ij(t_i, t_j) )
+ *   E_ij(a,b) = J_ij(a,b) - J_ij(a,t_j) - J_ij(t_i,b) + J_ij(t_i,t_j)
+ *   dH_h = sum_m S_h[i_m,a_m]   dH_J = sum_m S_J[i_m,a_m] + sum_{m<n} E_{i_m i_n}(a_m,a_n)   dH = dH_J + dH_h
+ * x_canonical: as plm_hamiltonians (float32); all arithmetic is float64, sums in a fixed order, no floating-point
+ * atomics: the same input gives the same bits.  Substituting the target's own letter adds 0; M = 0 gives (0, 0, 0).
+ *
+ * plm_mutant_effects: n_variants variants in CSR form, variant v holding the entries offsets[v] .. offsets[v+1]-1 of
+ * positions (0-based sites) and states; n_entries is the length of those two arrays.  out: n_variants x 3 doubles
+ * (dH, dH_J, dH_h); status: one byte per variant.  A malformed variant gets NaN in all three and the first of these
+ * codes that applies (the kernels check a variant before they load anything through its indices); the call still
+ * returns PLM_OK.  A repeated position is refused, where the reference counts it twice.
+ * tables_out, if not NULL: [n_sites][n_states][2] doubles (S_J, S_h), the single-mutant matrix in float64.
+ * PLM_EINVAL (before the device is looked at): NULL argument, n_sites < 2, n_variants or n_entries < 0, a target
+ * state outside 0..q-1, offsets[0] != 0, offsets decreasing, offsets[n_variants] != n_entries;
+ * PLM_EUNSUPPORTED: q outside 2..32. */
+#define PLM_MUT_OK 0
+#define PLM_MUT_ETOOMANY 1    /* more entries than the model has sites */
+#define PLM_MUT_EPOSITION 2   /* a position outside 0..n_sites-1 */
+#define PLM_MUT_ESTATE 3      /* a state outside 0..n_states-1 */
+#define PLM_MUT_EREPEAT 4     /* a position named twice */
+int plm_mutant_effects(const float *x_canonical, int32_t n_sites, int32_t n_states, const int8_t *target,
+                       int64_t n_variants, const int64_t *offsets, int64_t n_entries, const int32_t *positions,
+                       const int8_t *states, int device, void *stream, double *out, uint8_t *status,
+                       double *tables_out);
+
+/* plm_mutant_scan: every combination of letters at n_scan_sites (1..8) distinct sites.  Site s takes the letters
+ * letters[letter_offsets[s] .. letter_offsets[s+1]-1] (distinct states; letters == NULL: all n_states states at every
+ * site, in state order).  The combination index is mixed-radix with the last site fastest (the order of Python's
+ * itertools.product); the call covers the indices first .. first+count-1.  Outputs, each optional (NULL / 0):
+ *   energies    count x 3 doubles (dH, dH_J, dH_h)
+ *   histogram   n_edges+1 counts over the non-decreasing `edges` (at most 1024): a combination falls into the bin whose
+ *               number is the count of edges <= dH, found by comparison only (numpy.searchsorted(edges, dH, "right"))
+ *   dh_min, dh_max  exact extremes of dH over the range (+inf, -inf for count == 0); always written
+ *   kept_index, kept_energies  with use_threshold: the indices with dH >= threshold, ascending, and their energies, at
+ *               most `capacity` of them; n_kept is the number that qualified, and when it exceeds capacity the two
+ *               buffers are unspecified (call again with room for n_kept)
+ * The n_scan_sites single tables and the E tables of the site pairs are gathered once per call into compact tables
+ * that the scan reads through the caches.
+ * PLM_EINVAL: NULL argument, a site outside the model or named twice, an empty letter list, a letter outside 0..q-1 or
+ * named twice at a site, first or count < 0 or a range beyond the last combination, edges decreasing or NaN, more than
+ * 1024 edges, histogram without edges or edges without histogram, a NaN threshold, capacity < 0, capacity > 0 without
+ * the two buffers; PLM_EUNSUPPORTED: q outside 2..32, more than 8 sites, 2^62 combinations or more. */
+#define PLM_SCAN_MAX_SITES 8
+#define PLM_SCAN_MAX_EDGES 1024
+typedef struct {
+    int32_t n_scan_sites;
+    int32_t flags;                   /* 0 */
+    const int32_t *sites;            /* [n_scan_sites] */
+    const int32_t *letter_offsets;   /* [n_scan_sites + 1], read when letters != NULL */
+    const int8_t *letters;
+    int64_t first, count;
+    const double *edges;
+    int32_t n_edges;
+    int32_t use_threshold;
+    double threshold;
+    int64_t capacity;
+} plm_scan_opts;
+typedef struct {
+    double *energies;
+    uint64_t *histogram;
+    int64_t *kept_index;
+    double *kept_energies;
+    double dh_min, dh_max;
+    int64_t n_kept;
+    int64_t n_combinations;          /* of the whole library */
+} plm_scan_result;
+int plm_mutant_scan(const float *x_canonical, int32_t n_sites, int32_t n_states, const int8_t *target,
+                    const plm_scan_opts *opts, int device, void *stream, plm_scan_result *result);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
