@@ -260,6 +260,9 @@ SYMBOLS = [
                                     _P, _P, C.POINTER(C.c_uint64), C.c_int, _P]),
     ("plm_triplet_scan", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(PlmTripletOpts), _P,
                                    _P, _P, C.POINTER(C.c_uint64), C.c_int, _P]),
+    ("plm_residue_distances", C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int, _P]),
+    ("plm_distance_maps_aggregate", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
+                                              C.c_int32, _P, _P, C.c_int, _P]),
     ("plm_fasta_split", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P, _P]),
     ("plm_encode_columns", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("plm_write_raw_ec_file", C.c_int, [C.c_char_p, C.c_int32, _P, C.c_char_p, _P]),

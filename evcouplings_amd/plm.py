@@ -306,6 +306,65 @@ def triplet_scan(msa, q, weights=None, sites=None, skip_state=None, device=0, wi
     return out + (int(total.value),) if with_total else out
 
 
+def _atoms(coords, ranges, what):
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    ranges = np.ascontiguousarray(ranges, dtype=np.int32)
+    if coords.ndim != 2 or coords.shape[1] != 3:
+        raise ValueError("coords_%s must be an (atoms, 3) matrix, got shape %s" % (what, coords.shape))
+    if ranges.ndim != 2 or ranges.shape[1] != 2:
+        raise ValueError("ranges_%s must be a (residues, 2) matrix, got shape %s" % (what, ranges.shape))
+    return coords, ranges
+
+
+def residue_distances(coords_i, ranges_i, coords_j=None, ranges_j=None, device=0):
+    """
+    Minimum atom-atom distance between every residue of axis i and every residue of axis j, float64 (N_i, N_j):
+    coords (atoms, 3), ranges (residues, 2) = first and last atom of a residue, inclusive (ranges may overlap, skip
+    atoms, or be empty with last < first).  d2 = (dx dx + dy dy) + dz dz with every operation rounded once, the minimum
+    over the atom pairs, one correctly rounded square root, capped at 1e6 (also the value for a residue without
+    atoms): reproducible to the bit.  coords_j = ranges_j = None: axis i against itself, exactly symmetric.
+    """
+    lib = _lib.load()
+    ci, ri = _atoms(coords_i, ranges_i, "i")
+    if (coords_j is None) != (ranges_j is None):
+        raise ValueError("give both coords_j and ranges_j, or neither")
+    cj, rj = (None, None) if coords_j is None else _atoms(coords_j, ranges_j, "j")
+    n_j = len(ri) if rj is None else len(rj)
+    out = np.zeros((len(ri), n_j), np.float64)
+    check(lib.plm_residue_distances(_ptr(ci), len(ci), _ptr(ri), len(ri), _ptr(cj), 0 if cj is None else len(cj),
+                                    _ptr(rj), 0 if rj is None else len(rj), _ptr(out), int(device), None))
+    return out
+
+
+def aggregate_distance_maps(coords, ranges, chain_offsets, slots_i, maps, m_i, slots_j=None, m_j=None, agg=True,
+                            count=True, device=0):
+    """
+    The minimum of many residue distance maps on one pair of axes, without the stack of maps.  coords (atoms, 3) and
+    ranges (residues, 2; atom indices into `coords`) hold every chain one after the other, chain c owning the residues
+    chain_offsets[c] .. chain_offsets[c + 1] - 1.  slots_i / slots_j give every residue its row / column of the result
+    (-1: none; slots_j = None: slots_i on both axes, m_j = None: m_i), maps (S, 2) lists (chain on axis i, chain on
+    axis j).  Returns (agg, count): agg (m_i, m_j) float64, the minimum of `residue_distances` over the maps that cover
+    a cell and NaN where none does; count (m_i, m_j) int32, the number of maps that cover it.  agg=False / count=False
+    leaves that output out (None).
+    """
+    lib = _lib.load()
+    coords, ranges = _atoms(coords, ranges, "of the chains")
+    off = np.ascontiguousarray(chain_offsets, dtype=np.int32).reshape(-1)
+    maps = np.ascontiguousarray(maps, dtype=np.int32).reshape(-1, 2)
+    si = np.ascontiguousarray(slots_i, dtype=np.int32).reshape(-1)
+    sj = None if slots_j is None else np.ascontiguousarray(slots_j, dtype=np.int32).reshape(-1)
+    m_i = int(m_i)
+    m_j = m_i if m_j is None else int(m_j)
+    if len(off) < 2 or off[-1] != len(ranges) or len(si) != len(ranges) or (sj is not None and len(sj) != len(ranges)):
+        raise ValueError("chain_offsets must end at the %d residues, and the slots hold one entry per residue" % len(ranges))
+    shape = (max(m_i, 0), max(m_j, 0))
+    a = np.zeros(shape, np.float64) if agg else None
+    c = np.zeros(shape, np.int32) if count else None
+    check(lib.plm_distance_maps_aggregate(_ptr(coords), len(coords), _ptr(ranges), _ptr(off), len(off) - 1, _ptr(si),
+                                          _ptr(sj), m_i, m_j, _ptr(maps), len(maps), _ptr(a), _ptr(c), int(device), None))
+    return a, c
+
+
 def hamiltonians(seqs, q, hi, jij, device=0):
     """
     Statistical energies of sequences under a model: n x 3 float64 (H, H_J, H_h) with

@@ -97,19 +97,25 @@ def unregister_protocols():
         cp.PROTOCOLS.pop(name, None)
 
 
-def install_all(analysis=False, mutations=False):
+def install_all(analysis=False, mutations=False, structures=False):
     """run_plmc + the N2 / N3 / N4 drop-ins (model energies, alignment statistics, mean-field DCA); with `analysis`
     also CouplingsModel's EC scores, double-mutant matrix and independent model (model_accel.install(analysis=True));
-    with `mutations` also the mutate stage's predict_mutation_table (model_accel.install(mutations=True))."""
+    with `mutations` also the mutate stage's predict_mutation_table (model_accel.install(mutations=True)); with
+    `structures` also the compare stage's residue distance kernel (structure_accel.install())."""
     from evcouplings_amd import alignment_accel, mean_field, model_accel
     install()
     model_accel.install(analysis=analysis, mutations=mutations)
     mean_field.install()
     alignment_accel.install()
+    if structures:
+        from evcouplings_amd import structure_accel
+        structure_accel.install()
 
 
 def uninstall_all():
-    from evcouplings_amd import alignment_accel, mean_field, model_accel
+    from evcouplings_amd import alignment_accel, mean_field, model_accel, structure_accel
+    for module in list(structure_accel._ORIGINAL):
+        structure_accel.uninstall(module)
     alignment_accel.uninstall()
     mean_field.uninstall()
     model_accel.uninstall()

@@ -654,6 +654,41 @@ int plm_triplet_scan(const int8_t *msa, const float *weights, int32_t n_seqs, in
                      const int32_t *sites, int32_t n_sel, const plm_triplet_opts *opts, double *norm2, double *maxabs,
                      int32_t *argmax, uint64_t *total, int device, void *stream);
 
+/* ---- residue distance maps of structures, and their minimum over many chains -----------------------------------------
+ * The arithmetic of the reference's compare stage (_distances, compare/distances.py:24-88, and the minimum that
+ * DistanceMap.aggregate takes over a stack of maps), all in float64.  For a residue pair (i, j):
+ *   d2(a, b)  = (dx dx + dy dy) + dz dz over the atoms a of i and b of j, dx = x_a - x_b and so on; every difference,
+ *               product and sum is rounded once (no fused multiply-add);
+ *   dist(i,j) = min(1e6, sqrt(min over (a, b) of d2)), one correctly rounded square root (sqrt is monotone: this is the
+ *               minimum of the distances).  1e6 is the reference's LARGE_DIST; a residue without atoms yields it too.
+ * A minimum of correctly rounded values: no output bit depends on the launch plan.  PLM_DIST_PLAN forces the plan
+ * (measurements and tests): a comma-separated list of t<int> (residues on the row side of a workgroup's tile: 4, 8, 16,
+ * 32 or 64; the column side is 256 / t) and c<int> (atoms of a residue per staging chunk, 1..32).
+ * plm_residue_distances: coords [n_atoms][3]; ranges [n_res][2] int32, the first and last atom of a residue, inclusive;
+ *   ranges may overlap, leave atoms out, and be empty (last < first, whatever the two values are).  coords_j == NULL and
+ *   ranges_j == NULL (n_atoms_j, n_res_j ignored): the symmetric call on axis i alone; only the pairs i <= j are
+ *   computed and stored at both places, so the output is exactly symmetric, and equal bit for bit to the call with the
+ *   chain on both axes.  dist_out [n_res_i][n_res_j].
+ * plm_distance_maps_aggregate: n_chains chains in one coordinate array and one range array (atom indices count from
+ *   the start of the coordinate array); chain c owns the residues chain_offsets[c] .. chain_offsets[c + 1] - 1
+ *   (chain_offsets [n_chains + 1], ascending from 0).  slots_i / slots_j [residues]: the row / column of a residue in
+ *   the aggregated map, -1 = not in it; slots_j == NULL: slots_i serves both axes.  maps [n_maps][2]: (chain on axis i,
+ *   chain on axis j); a chain may be on both axes and in any number of maps.  agg [m_i][m_j]: the minimum of dist over
+ *   the maps that cover the cell, NaN where none does; count [m_i][m_j] int32: how many do.  Either may be NULL.  No
+ *   n_maps x m_i x m_j array is made: device memory is the inputs plus the outputs.
+ * PLM_EINVAL (with a message, before the device is looked at): NULL inputs; only one of coords_j / ranges_j; sizes
+ * below 1; a non-empty range that reaches outside the atoms; a coordinate that is not finite; more than 65535 tiles of
+ * rows; chain offsets that do not ascend from 0 or hold no residue; a slot outside -1..m-1; two residues of one chain at
+ * one slot of an axis; a chain index outside 0..n_chains-1; more than 2^31 - 1 tiles in all; a malformed PLM_DIST_PLAN.
+ * PLM_ENOMEM before any allocation.                                                                                  */
+int plm_residue_distances(const double *coords_i, int32_t n_atoms_i, const int32_t *ranges_i, int32_t n_res_i,
+                          const double *coords_j, int32_t n_atoms_j, const int32_t *ranges_j, int32_t n_res_j,
+                          double *dist_out, int device, void *stream);
+int plm_distance_maps_aggregate(const double *coords, int32_t n_atoms, const int32_t *ranges, const int32_t *chain_offsets,
+                                int32_t n_chains, const int32_t *slots_i, const int32_t *slots_j, int32_t m_i, int32_t m_j,
+                                const int32_t *maps, int32_t n_maps, double *agg, int32_t *count, int device,
+                                void *stream);
+
 /* ---- alignment input (host code, no device): what plmc does when it reads the file run_plmc names (tools.py:202-262
  * passes only the path).  evcouplings_amd/alignment_io.py states the rules and keeps a pure-Python twin (fallback and
  * test oracle); these two single passes replace its per-line loop and fancy indexing (0.23 -> 0.03 s at the headline).
