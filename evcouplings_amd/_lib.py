@@ -210,6 +210,21 @@ class PlmScanResult(C.Structure):
     ]
 
 
+class PlmArSampleOpts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("first_chain", C.c_uint32), ("seed", C.c_uint64), ("beta", C.c_float),
+                ("allowed", C.c_void_p)]
+
+
+class PlmArFitOpts(C.Structure):
+    _fields_ = [("lambda_h", C.c_double), ("lambda_j", C.c_double), ("max_iter", C.c_int32), ("epsilon", C.c_double),
+                ("lbfgs_m", C.c_int32)]
+
+
+class PlmArFitResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("ls_reason", C.c_int32),
+                ("fx", C.c_double), ("nll", C.c_double), ("gnorm", C.c_double), ("xnorm", C.c_double)]
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -310,6 +325,12 @@ SYMBOLS = [
                                      _P]),
     ("plm_mutant_scan", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(PlmScanOpts), C.c_int, _P,
                                   C.POINTER(PlmScanResult)]),
+    ("plm_ar_logprob", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int, _P, _P, _P]),
+    ("plm_ar_sample", C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(PlmArSampleOpts), C.c_int, _P, _P]),
+    ("plm_ar_eval", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int, _P,
+                              C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    ("plm_ar_fit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmArFitOpts), _P, ITER_CB, _P, C.c_int,
+                             _P, _P, C.POINTER(PlmArFitResult)]),
 ]
 
 _lib = None

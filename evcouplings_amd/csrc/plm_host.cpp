@@ -1262,34 +1262,6 @@ static int ctx_build_dinv(plm_ctx_t *c) {
     PLM_HIP(hipStreamSynchronize(c->st));   // fv leaves scope
     return PLM_OK;
 }
-// Basis and flags of the Gram pass (queries s_new, y_new, g): S[0..nst), Y[0..nst), g, g.  Products in the H0 metric:
-// the Y's and the first g on the basis side (wb), y_new and g on the query side (wq); the second g stays unweighted
-// (g.g for the stop rule).
-static void lbfgs_gram_basis(const float *S, const float *Y, const float *g, int64_t n, int nst, PlmVecList *B,
-                             unsigned long long *wb_out, unsigned *wq_out) {
-    B->n = 0;
-    for (int i = 0; i < nst; i++) B->v[B->n++] = S + (size_t)i * n;
-    unsigned long long wb = 0;
-    for (int i = 0; i < nst; i++) { wb |= 1ull << B->n; B->v[B->n++] = Y + (size_t)i * n; }
-    wb |= 1ull << B->n;
-    B->v[B->n++] = g;
-    B->v[B->n++] = g;
-    *wb_out = wb;
-    *wq_out = 6u;
-}
-// Basis and coefficients of the direction p = sum cs[j] s_j + D^-1 (sum cy[j] y_j + cg g) over the LIVE pairs, the
-// `stored` ring slots before `end`, newest first; returns the index of the first vector under D^-1.
-static int lbfgs_direction_basis(const float *S, const float *Y, const float *g, int64_t n, int m, int stored, int end,
-                                 const double *cs, const double *cy, double cg, PlmVecList *B, PlmCoefList *C) {
-    B->n = 0;
-    for (int i = 0; i < stored; i++) { const int j = lbfgs_live_slot(m, end, i); B->v[B->n] = S + (size_t)j * n; C->c[B->n++] = (float)cs[j]; }
-    const int first_weighted = B->n;
-    for (int i = 0; i < stored; i++) { const int j = lbfgs_live_slot(m, end, i); B->v[B->n] = Y + (size_t)j * n; C->c[B->n++] = (float)cy[j]; }
-    B->v[B->n] = g;
-    C->c[B->n++] = (float)cg;
-    return first_weighted;
-}
-
 // L-BFGS with a More'-Thuente line search; vectors stay in HBM, only scalars cross PCIe.
 // Defaults follow libLBFGS (m = 6, ftol 1e-4, gtol 0.9, <= 20 trial steps), which plmc bundles
 // [recollection, SURVEY.md App. C.4].  The two-loop recursion (Nocedal 1980) is evaluated in

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <hip/hip_runtime.h>
+#include "plm_lbfgs.h"
 
 #define PLM_MAX_SHARDS 16     // sharded-state mode: shards of one problem (PlmDims carries a table per partner)
 #define PLM_PAD_STATE 127
@@ -379,6 +380,34 @@ struct PlmCoefList {
 // dinv != nullptr: the basis vectors from index `first_weighted` on are summed separately and multiplied by dinv
 hipError_t plm_launch_multiaxpy(float *out, const PlmVecList &basis, const PlmCoefList &coef, int64_t n,
                                 const float *dinv, int first_weighted, hipStream_t st);
+// The basis order of the two passes of an L-BFGS iteration, once for every driver (plm_ctx_optimize, plm_ar_fit).
+// Basis and flags of the Gram pass (queries s_new, y_new, g): S[0..nst), Y[0..nst), g, g.  Products in the H0 metric:
+// the Y's and the first g on the basis side (wb), y_new and g on the query side (wq); the second g stays unweighted
+// (g.g for the stop rule).
+inline void lbfgs_gram_basis(const float *S, const float *Y, const float *g, int64_t n, int nst, PlmVecList *B,
+                             unsigned long long *wb_out, unsigned *wq_out) {
+    B->n = 0;
+    for (int i = 0; i < nst; i++) B->v[B->n++] = S + (size_t)i * n;
+    unsigned long long wb = 0;
+    for (int i = 0; i < nst; i++) { wb |= 1ull << B->n; B->v[B->n++] = Y + (size_t)i * n; }
+    wb |= 1ull << B->n;
+    B->v[B->n++] = g;
+    B->v[B->n++] = g;
+    *wb_out = wb;
+    *wq_out = 6u;
+}
+// Basis and coefficients of the direction p = sum cs[j] s_j + D^-1 (sum cy[j] y_j + cg g) over the LIVE pairs, the
+// `stored` ring slots before `end`, newest first; returns the index of the first vector under D^-1.
+inline int lbfgs_direction_basis(const float *S, const float *Y, const float *g, int64_t n, int m, int stored, int end,
+                                 const double *cs, const double *cy, double cg, PlmVecList *B, PlmCoefList *C) {
+    B->n = 0;
+    for (int i = 0; i < stored; i++) { const int j = lbfgs_live_slot(m, end, i); B->v[B->n] = S + (size_t)j * n; C->c[B->n++] = (float)cs[j]; }
+    const int first_weighted = B->n;
+    for (int i = 0; i < stored; i++) { const int j = lbfgs_live_slot(m, end, i); B->v[B->n] = Y + (size_t)j * n; C->c[B->n++] = (float)cy[j]; }
+    B->v[B->n] = g;
+    C->c[B->n++] = (float)cg;
+    return first_weighted;
+}
 // inverse Hessian diagonal of the independent-site model in the native layout; fv = [f | p(1-p)], 2*L*Q floats
 hipError_t plm_launch_precond(const PlmDims &d, const float *fv, float neff, float lambda_h, float lambda_j, float *dinv,
                               hipStream_t st);

@@ -416,6 +416,105 @@ def sample(hi, jij, q, n_chains, burn_in=10, n_snapshots=1, thin=1, beta=1.0, se
     return samples, en
 
 
+def _split_canonical(x, L, q):
+    return x[:L * q].reshape(L, q), x[L * q:].reshape(L * (L - 1) // 2, q, q)
+
+
+def ar_logprob(seqs, q, hi, jij, site_terms=False, device=0):
+    """
+    Exact log-probabilities under an autoregressive Potts model (plm_ar_logprob, DESIGN_NEXT_ROWS.md section 9.19):
+    P(x) = prod_i softmax_b(h_i(b) + sum_{j<i} J_ji(x_j, b)) at b = x_i.  hi: L x q; jij: the i<j blocks, entry [a][b] of
+    block (j, i) coupling state a of the earlier site j with state b of the later site i.
+    Returns log P [n] (float64), with site_terms also the site terms [n, L] that sum to it.
+    """
+    q = int(q)
+    hi, jij, L = _potts_model(hi, jij, q)
+    seqs = _msa(seqs)
+    if seqs.shape[1] != L:
+        raise ValueError("the sequences have %d sites, the model %d" % (seqs.shape[1], L))
+    n = seqs.shape[0]
+    logp = np.zeros(n)
+    site = np.zeros((n, L)) if site_terms else None
+    check(_lib.load().plm_ar_logprob(_ptr(seqs), n, L, q, _ptr(_canonical(hi, jij, L, q)), int(device), None, _ptr(logp),
+                                     _ptr(site)))
+    return (logp, site) if site_terms else logp
+
+
+def ar_sample(hi, jij, q, n, seed=0, beta=1.0, allowed=None, first_chain=0, device=0):
+    """
+    n independent exact samples of an autoregressive Potts model, one ancestral pass each (plm_ar_sample): int8 [n, L].
+    Sample c of a call is chain first_chain + c of the seed, whatever n.  allowed: None or q flags of the states that may
+    be drawn; beta: inverse temperature of every conditional.
+    """
+    q, n = int(q), int(n)
+    hi, jij, L = _potts_model(hi, jij, q)
+    _, _, allowed = _chain_args(None, None, allowed, n, L, q)
+    opts = _lib.PlmArSampleOpts(n, int(first_chain) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, float(beta), _ptr(allowed))
+    out = np.zeros((max(n, 0), L), dtype=np.int8)
+    check(_lib.load().plm_ar_sample(L, q, _ptr(_canonical(hi, jij, L, q)), C.byref(opts), int(device), None, _ptr(out)))
+    return out
+
+
+def ar_evaluate(msa, weights, q, lambda_h, lambda_j, hi, jij, device=0):
+    """
+    F = -(1/N_eff) sum_s w_s log P(x_s) + lambda_h sum h^2 + lambda_j sum J^2 of an autoregressive Potts model, its first
+    term and the float64 gradient (plm_ar_eval).  Returns (F, nll, g_h [L, q], g_J [pairs, q, q]).
+    """
+    q = int(q)
+    hi, jij, L = _potts_model(hi, jij, q)
+    msa = _msa(msa)
+    if msa.shape[1] != L:
+        raise ValueError("the alignment has %d sites, the model %d" % (msa.shape[1], L))
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.shape != (msa.shape[0],):
+        raise ValueError("need one weight per sequence")
+    g = np.zeros(n_params(L, q))
+    fx, nll = C.c_double(0), C.c_double(0)
+    check(_lib.load().plm_ar_eval(_ptr(msa), _ptr(w), msa.shape[0], L, q, float(lambda_h), float(lambda_j),
+                                  _ptr(_canonical(hi, jij, L, q)), int(device), None, C.byref(fx), C.byref(nll), _ptr(g)))
+    g_h, g_j = _split_canonical(g, L, q)
+    return fx.value, nll.value, g_h, g_j
+
+
+AR_STATUS = {_lib.STATUS_CONVERGED: "converged", _lib.STATUS_MAXITER: "maxiter", _lib.STATUS_LINESEARCH: "linesearch",
+             _lib.STATUS_INTERRUPTED: "interrupted"}
+
+
+def ar_fit(msa, weights, q, lambda_h, lambda_j, max_iter=1000, epsilon=1e-4, lbfgs_m=6, start=None, callback=None,
+           device=0):
+    """
+    Fit an autoregressive Potts model to a weighted alignment by L-BFGS on the device (plm_ar_fit).  lambda_h, lambda_j:
+    per-sequence units (F is normalised by N_eff).  start: None (zeros) or (hi, jij).  callback(iter, seconds, cond, fx,
+    nll, |h|, |J|) is called after every iteration; a true return value stops the fit ("interrupted").
+    Returns a dict: hi [L, q], jij [pairs, q, q] (float32), status (one of AR_STATUS's values), iterations, evaluations,
+    ls_reason, fx, nll, gnorm, xnorm.
+    """
+    q = int(q)
+    msa = _msa(msa)
+    n, L = msa.shape
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.shape != (n,):
+        raise ValueError("need one weight per sequence")
+    x0 = None
+    if start is not None:
+        hi, jij, Ls = _potts_model(start[0], start[1], q)
+        if Ls != L:
+            raise ValueError("the start point has %d sites, the alignment %d" % (Ls, L))
+        x0 = _canonical(hi, jij, L, q)
+    cb, reraise = _stop_callback(_lib.ITER_CB, callback, convert=lambda *a: a)
+    opts = _lib.PlmArFitOpts(float(lambda_h), float(lambda_j), int(max_iter), float(epsilon), int(lbfgs_m))
+    res = _lib.PlmArFitResult()
+    x = np.zeros(max(n_params(L, q), 1), dtype=np.float32)
+    rc = _lib.load().plm_ar_fit(_ptr(msa), _ptr(w), n, L, q, C.byref(opts), _ptr(x0), cb, None, int(device), None, _ptr(x),
+                                C.byref(res))
+    reraise()
+    check(rc)
+    hi, jij = _split_canonical(x[:n_params(L, q)], L, q)
+    return {"hi": hi, "jij": jij, "status": AR_STATUS[res.status], "iterations": res.iterations,
+            "evaluations": res.evaluations, "ls_reason": res.ls_reason, "fx": res.fx, "nll": res.nll, "gnorm": res.gnorm,
+            "xnorm": res.xnorm}
+
+
 def sample_plan(L, q, n_chains, n_cu=0):
     """
     The launch plan `sample` and `bm_fit` use for L sites, q states and n_chains chains (plm_sample_plan,

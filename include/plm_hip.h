@@ -960,6 +960,84 @@ typedef struct {
 int plm_mutant_scan(const float *x_canonical, int32_t n_sites, int32_t n_states, const int8_t *target,
                     const plm_scan_opts *opts, int device, void *stream, plm_scan_result *result);
 
+/* ---- The autoregressive Potts model (DESIGN_NEXT_ROWS.md section 9.19) -------------------------------------------------
+ *     P(x) = prod_i P(x_i | x_<i),   P(x_i = b | x_<i) = softmax_b( h_i(b) + sum_{j<i} J_ji(x_j, b) )
+ * (arDCA, Trinquier et al. 2021).  It is normalised by construction: log P(x) is exact, a sample is one pass over the
+ * sites, and the fit is a convex problem with exact gradients.
+ *
+ * Parameters: float32 in the canonical layout of plm_hamiltonians, h [L][q], then the i<j blocks [q][q].  Block (j, i)
+ * with j < i sits at the canonical pair index of (j, i); its entry [a][b] couples state a of the EARLIER site j with
+ * state b of the LATER site i, and the block enters the conditional of site i only (h_0 alone is the first site's
+ * conditional).  These are NOT the symmetric-gauge couplings of a Potts model and must not be read as one.  The sites
+ * are taken in the order 0 .. L-1; another order is a permutation of the columns by the caller.
+ * q in 2..32 (PLM_EUNSUPPORTED otherwise), L >= 1.  In all four calls the arguments are checked before the device is
+ * looked at (PLM_EINVAL: NULL arguments, sizes below 1, n x L at or above 2^31, states outside 0..q-1 and what each call
+ * names below), and PLM_ENOMEM is decided before any allocation.
+ *
+ * plm_ar_logprob: logp_out [n] = log P of each sequence, site_logp_out [n][L] (or NULL) its site terms.  logit_b is
+ *   accumulated in float64 from (double) h_i(b) over j = 0 .. i-1 in that order; the log-softmax is taken in float64 (the
+ *   maximum, then the sum of exp in state order); log P is the sum of the site terms in site order.  The result depends
+ *   on (sequence, model) only, not on n or the place of the sequence in the call.
+ *
+ * plm_ar_sample: states_out [n_samples][L], one ancestral pass per chain.  Site i of chain c: U_b starts as h_i(b) in
+ *   float32 and takes one float32 add per j = 0 .. i-1, in that order, of J_ji(x_cj, b); the new state is the draw of
+ *   plm_sample's contract (e_b = exp(beta U_b - max) over the allowed states in state order, the first allowed state
+ *   whose running sum exceeds u S_last) with the Philox4x32-10 counter (first_chain + c, 0, 0, i) and the key
+ *   (seed low, seed high).  Chain c of any call is the same chain whatever n_samples and however a run is cut into calls
+ *   by first_chain.  beta must be finite and > 0; allowed is NULL or q flags, one set at least.  There are no fixed
+ *   sites: an autoregressive pass conditions a site on the EARLIER sites only, so fixing a later site would not give
+ *   samples of the conditional distribution (that needs the posterior over the earlier sites, which this model does not
+ *   factorise).
+ *
+ * plm_ar_eval: F(x) = -(1/N_eff) sum_s w_s log P(x_s) + lambda_h sum h^2 + lambda_j sum J^2, N_eff = sum_s w_s summed in
+ *   float64 in sequence order; nll_out (or NULL) is the first term; g_out (or NULL) the gradient, canonical, double:
+ *     dF/dh_i(b)     = -(1/N_eff) sum_s w_s (delta(x_si, b) - p_sib) + 2 lambda_h h_i(b)
+ *     dF/dJ_ji(a, b) = -(1/N_eff) sum_s w_s delta(x_sj, a) (delta(x_si, b) - p_sib) + 2 lambda_j J_ji(a, b)
+ *   Logits, probabilities, residuals and every sum over sequences are float64, in an order the shape alone fixes, without
+ *   floating-point atomics: two calls return the same bytes.  The division by N_eff follows the sum.  PLM_EINVAL for a
+ *   weight that is negative or not finite, for weights that sum to zero and for a negative lambda.
+ *
+ * plm_ar_fit: minimises F over float32 parameters by L-BFGS (More'-Thuente line search, lbfgs_m pairs) from x_start
+ *   (NULL: zeros); lambda_h and lambda_j are in per-sequence units, as F is normalised by N_eff.  The gradient is rounded
+ *   to float32 once, where it enters the pair history; f, the directional derivatives of the line search and the norms of
+ *   the stop rule come from the float64 evaluation.  Status: PLM_STATUS_CONVERGED when |g|_2 <= epsilon max(1, |x|_2) at
+ *   the float32 point that is returned, PLM_STATUS_MAXITER after max_iter iterations (0: no limit),
+ *   PLM_STATUS_LINESEARCH (ls_reason: the line search's code, 10 for a direction that does not descend),
+ *   PLM_STATUS_INTERRUPTED when the callback returned non-zero (x_out is the point of that iteration).  The callback's
+ *   arguments are those of plm_fit's.  PLM_EINVAL also for max_iter < 0, an epsilon that is not finite and > 0, lbfgs_m
+ *   outside 1..20. */
+typedef struct {
+    int32_t  n_samples;        /* >= 1 */
+    uint32_t first_chain;      /* the chain index of the call's first sample */
+    uint64_t seed;
+    float    beta;             /* > 0 */
+    const uint8_t *allowed;    /* [q] flags or NULL */
+} plm_ar_sample_opts;
+typedef struct {
+    double  lambda_h, lambda_j;
+    int32_t max_iter;          /* 0: no limit */
+    double  epsilon;
+    int32_t lbfgs_m;           /* 1..20 */
+} plm_ar_fit_opts;
+typedef struct {
+    int32_t status;            /* PLM_STATUS_* */
+    int32_t iterations;
+    int32_t evaluations;
+    int32_t ls_reason;         /* with PLM_STATUS_LINESEARCH, else 0 */
+    double  fx, nll;           /* F and its first term at x_out */
+    double  gnorm, xnorm;      /* |g|_2 and |x|_2 at x_out */
+} plm_ar_fit_result;
+int plm_ar_logprob(const int8_t *seqs, int32_t n_seqs, int32_t n_sites, int32_t n_states, const float *x_canonical,
+                   int device, void *stream, double *logp_out, double *site_logp_out);
+int plm_ar_sample(int32_t n_sites, int32_t n_states, const float *x_canonical, const plm_ar_sample_opts *opts, int device,
+                  void *stream, int8_t *states_out);
+int plm_ar_eval(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
+                double lambda_h, double lambda_j, const float *x_canonical, int device, void *stream, double *fx_out,
+                double *nll_out, double *g_out);
+int plm_ar_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
+               const plm_ar_fit_opts *opts, const float *x_start, plm_iter_cb cb, void *user, int device, void *stream,
+               float *x_out, plm_ar_fit_result *result);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
