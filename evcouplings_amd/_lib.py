@@ -166,6 +166,13 @@ class PlmTripletOpts(C.Structure):
     _fields_ = [("skip_state", C.c_int32), ("want", C.c_int32)]
 
 
+class PlmPcaOpts(C.Structure):
+    _fields_ = [("n_components", C.c_int32), ("oversample", C.c_int32), ("max_iter", C.c_int32),
+                ("skip_state", C.c_int32), ("tol", C.c_double), ("seed", C.c_uint64)]
+
+
+PCA_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_double, C.c_void_p)
+
 FIELD_ROLE_STATS, FIELD_ROLE_HESSIAN, FIELD_ROLE_RESIDUAL = 0, 1, 2
 FIELD_HIST, FIELD_MAXBLK = 24, 256
 
@@ -275,6 +282,13 @@ SYMBOLS = [
                                     _P, _P, C.POINTER(C.c_uint64), C.c_int, _P]),
     ("plm_triplet_scan", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(PlmTripletOpts), _P,
                                    _P, _P, C.POINTER(C.c_uint64), C.c_int, _P]),
+    ("plm_pca_fit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmPcaOpts), _P, _P, _P, _P,
+                              C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P,
+                              C.c_int, _P]),
+    ("plm_pca_fit_cb", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmPcaOpts), _P, _P, _P, _P,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 _P, C.c_int, _P, PCA_CB, _P, C.POINTER(C.c_int32)]),
+    ("plm_pca_project", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int, _P]),
     ("plm_residue_distances", C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int, _P]),
     ("plm_distance_maps_aggregate", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
                                               C.c_int32, _P, _P, C.c_int, _P]),

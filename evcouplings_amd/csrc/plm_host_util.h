@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 int plm_fail(int code, const char *fmt, ...);   // plm_host.cpp: records the message for plm_last_error()
@@ -91,6 +92,35 @@ inline int plm_check_free(double need_bytes, const char *what, double table_byte
 inline double plm_n_canon(int L, int q) { return (double)L * q + (double)L * (L - 1) / 2 * q * q; }
 
 inline uint32_t plm_state_mask(int q) { return q == 32 ? 0xFFFFFFFFu : (1u << q) - 1u; }   // states 0 .. q-1
+
+// The fixed-point weights of the alignment statistics (include/plm_hip.h, three-site section): e = the largest integer
+// <= 30 with max(w) 2^e <= 2^30, wq_n = llrint((double)w_n 2^e), W = sum wq_n.  wq: `padded` entries (>= N, the rest 0);
+// weights == NULL: wq is left empty (every weight is 1) and W = N.  PLM_EINVAL for a weight that is negative or not
+// finite, and for W = 0.
+inline int plm_quantise_weights(const float *weights, int N, size_t padded, std::vector<uint32_t> *wq, uint64_t *W) {
+    wq->clear();
+    *W = (uint64_t)N;
+    if (!weights) return PLM_OK;
+    double wmax = 0.0;
+    for (int n = 0; n < N; n++) {
+        const double w = (double)weights[n];
+        if (!std::isfinite(w) || w < 0.0) return plm_fail(PLM_EINVAL, "weights[%d] = %g is negative or not finite", n, w);
+        wmax = std::max(wmax, w);
+    }
+    if (!(wmax > 0.0)) return plm_fail(PLM_EINVAL, "the weights are all zero (W = 0)");
+    int e = 30;                                   // the largest e <= 30 with wmax 2^e <= 2^30
+    while (std::ldexp(wmax, e) > 1073741824.0) e--;
+    wq->assign(padded, 0u);
+    uint64_t sum = 0;
+    for (int n = 0; n < N; n++) {
+        const long long v = llrint(std::ldexp((double)weights[n], e));
+        (*wq)[n] = (uint32_t)v;
+        sum += (uint64_t)v;
+    }
+    if (sum == 0) return plm_fail(PLM_EINVAL, "the fixed-point weights are all zero (W = 0)");
+    *W = sum;
+    return PLM_OK;
+}
 
 // The padded row-major host image of n sequences of L states that the forward kernels read: rows of row_len bytes,
 // n_rows of them, `pad` wherever no sequence is.

@@ -247,28 +247,9 @@ int trip_image(const int8_t *msa, const float *weights, int N, int L, int q, con
     if ((long long)N + 16 > INT_MAX) return plm_fail(PLM_EINVAL, "n_seqs %d is too large", N);
     im->N = N; im->n_cols = n_cols; im->q = q;
     im->Np = ((size_t)N + 15) / 16 * 16;
-    im->wq.clear();
-    im->W = (u64)N;
-    if (weights) {
-        double wmax = 0.0;
-        for (int n = 0; n < N; n++) {
-            const double w = (double)weights[n];
-            if (!std::isfinite(w) || w < 0.0) return plm_fail(PLM_EINVAL, "weights[%d] = %g is negative or not finite", n, w);
-            wmax = std::max(wmax, w);
-        }
-        if (!(wmax > 0.0)) return plm_fail(PLM_EINVAL, "the weights are all zero (W = 0)");
-        int e = 30;                                   // the largest e <= 30 with wmax 2^e <= 2^30
-        while (std::ldexp(wmax, e) > 1073741824.0) e--;
-        im->wq.assign(im->Np, 0u);
-        u64 W = 0;
-        for (int n = 0; n < N; n++) {
-            const long long v = llrint(std::ldexp((double)weights[n], e));
-            im->wq[n] = (u32)v;
-            W += (u64)v;
-        }
-        if (W == 0) return plm_fail(PLM_EINVAL, "the fixed-point weights are all zero (W = 0)");
-        im->W = W;
-    }
+    uint64_t W = 0;
+    PLM_TRY(plm_quantise_weights(weights, N, im->Np, &im->wq, &W));
+    im->W = W;
     for (int n = 0; n < N; n++)
         for (int i = 0; i < L; i++) {
             const int8_t v = msa[(size_t)n * L + i];

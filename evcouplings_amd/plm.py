@@ -306,6 +306,67 @@ def triplet_scan(msa, q, weights=None, sites=None, skip_state=None, device=0, wi
     return out + (int(total.value),) if with_total else out
 
 
+PCA_STATUS = {_lib.STATUS_CONVERGED: "converged", _lib.STATUS_MAXITER: "maxiter", _lib.STATUS_INTERRUPTED: "interrupted"}
+
+
+def pca_fit(msa, q, k=2, weights=None, skip_state=None, oversample=8, max_iter=500, tol=1e-10, seed=0, scores=False,
+            device=0, callback=None):
+    """
+    The k leading principal components of the centred one-hot features of an alignment (N x L states 0..q-1), by block
+    subspace iteration on the GPU; the covariance is never formed (include/plm_hip.h states the definitions).  `weights`:
+    N non-negative floats, quantised as for `triplet_stats`; `skip_state`: a state whose features are left out.
+    Returns a dict: mean (L,q) = f_i(a), components (k,L,q) orthonormal with zeros at the skipped state, eigenvalues (k,)
+    descending, explained = eigenvalues / total_variance, total_variance = trace of the covariance, residuals (k,) =
+    |C v - lambda v|, iterations, converged (residuals <= tol lambda_1), status, total (W) and, with scores=True, scores
+    (N,k), the projections of the rows themselves.  callback(iteration, largest relative residual) is called once per
+    iteration; a true return value stops the fit ("interrupted").  Running out of iterations is a result, not an error.
+    """
+    lib = _lib.load()
+    msa = _msa(msa)
+    N, L = msa.shape
+    q, k = int(q), int(k)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+    if w is not None and w.shape != (N,):
+        raise ValueError("weights must hold one value per sequence (%d), got shape %s" % (N, w.shape))
+    opts = _lib.PlmPcaOpts(k, int(oversample), int(max_iter), -1 if skip_state is None else int(skip_state), float(tol),
+                           int(seed) & 0xFFFFFFFFFFFFFFFF)
+    kk, qq = (k if 1 <= k <= 64 else 0), (q if 2 <= q <= 32 else 0)
+    out = {"mean": np.zeros((L, qq)), "components": np.zeros((kk, L, qq)), "eigenvalues": np.zeros(kk),
+           "residuals": np.zeros(kk), "scores": np.zeros((N, kk)) if scores else None}
+    tv, total, its, conv, status = C.c_double(0), C.c_uint64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    cb, reraise = _stop_callback(_lib.PCA_CB, callback, lambda it, worst: (int(it), float(worst)))
+    check(lib.plm_pca_fit_cb(_ptr(msa), _ptr(w), N, L, q, C.byref(opts), _ptr(out["mean"]), _ptr(out["components"]),
+                             _ptr(out["eigenvalues"]), _ptr(out["residuals"]), C.byref(tv), C.byref(total), C.byref(its),
+                             C.byref(conv), _ptr(out["scores"]), int(device), None, cb, None, C.byref(status)))
+    reraise()
+    out.update(total_variance=tv.value, total=int(total.value), iterations=int(its.value), converged=bool(conv.value),
+               status=PCA_STATUS[int(status.value)],
+               explained=out["eigenvalues"] / tv.value if tv.value > 0 else np.zeros(kk))
+    return {key: v for key, v in out.items() if v is not None}
+
+
+def pca_project(seqs, q, mean, components, skip_state=None, device=0):
+    """
+    Projections (n,k) float64 of n sequences (n x L states 0..q-1) on the components (k,L,q) of `pca_fit` with its mean
+    (L,q): t_c(x) = sum_i v_c[i, x_i] - sum_{i,a} mean[i,a] v_c[i,a]; a skipped state contributes 0.
+    """
+    lib = _lib.load()
+    seqs = _msa(seqs)
+    n, L = seqs.shape
+    q = int(q)
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    components = np.ascontiguousarray(components, dtype=np.float64)
+    if mean.shape != (L, q):
+        raise ValueError("mean must be an (L, q) = (%d, %d) matrix, got shape %s" % (L, q, mean.shape))
+    if components.ndim != 3 or components.shape[1:] != (L, q):
+        raise ValueError("components must be (k, %d, %d), got shape %s" % (L, q, components.shape))
+    k = components.shape[0]
+    out = np.zeros((n, k if 1 <= k <= 64 else 0))
+    check(lib.plm_pca_project(_ptr(seqs), n, L, q, _ptr(mean), _ptr(components), k, -1 if skip_state is None else int(skip_state),
+                              _ptr(out), int(device), None))
+    return out
+
+
 def _atoms(coords, ranges, what):
     coords = np.ascontiguousarray(coords, dtype=np.float64)
     ranges = np.ascontiguousarray(ranges, dtype=np.int32)

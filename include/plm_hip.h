@@ -654,6 +654,66 @@ int plm_triplet_scan(const int8_t *msa, const float *weights, int32_t n_seqs, in
                      const int32_t *sites, int32_t n_sel, const plm_triplet_opts *opts, double *norm2, double *maxabs,
                      int32_t *argmax, uint64_t *total, int device, void *stream);
 
+/* ---- principal components of an alignment, and projections on them ------------------------------------------------------
+ * msa, weights, wq_n and W as in the three-site section above (same quantisation rule, same errors; n_sites >= 1 here).
+ *   f_i(a)       = count_i(a) / W in float64, count_i(a) = sum_n wq_n [x_ni = a] an exact integer; returned in mean [L][q];
+ *   phi_n[(i,a)] = [x_ni = a] - f_i(a) for every site i and every state a != skip_state (skip_state = -1 keeps all
+ *                  states): D = L q or L (q - 1) features;
+ *   C            = (1/W) sum_n wq_n phi_n phi_n^T, never formed;  total_variance = trace C = sum f_i(a) (1 - f_i(a)) over
+ *                  the kept features, from the counts;
+ *   eigenvalues  lambda_1 >= ... >= lambda_k, the k largest of C, with orthonormal eigenvectors components [k][L][q] in
+ *                  float64 (zeros at the skipped state); the entry of a component with the largest magnitude is positive
+ *                  (the smallest index of a tie decides);
+ *   t_c(x)       = sum_i v_c[(i, x_i)] - sum_{i,a} f_i(a) v_c[(i,a)], the projection of a sequence x; a skipped state
+ *                  contributes 0.  scores [n][k].
+ * Method: block subspace iteration with a Rayleigh-Ritz step in float64; b = min(k + oversample, D, 64) columns started
+ * from Philox4x32-10 numbers keyed by (seed, feature, column).  An iteration computes U = Phi V and Y = Phi^T diag(wq) U / W,
+ * the b x b matrices V^T Y, V^T V, Y^T Y on the device, the b x b eigenproblems on the host (Jacobi), the rotation to the
+ * Ritz vectors and the next orthonormal block on the device; one host synchronisation per iteration.  The residuals
+ * |C v_c - theta_c v_c| of the Ritz vectors of an iteration are summed directly by the rotation and read with the next
+ * iteration's matrices; the loop stops when they are <= tol theta_1 for the first k columns, or after max_iter block
+ * products (iterations counts them).  Then the k vectors are made orthonormal to rounding (Gram-Schmidt, twice) and
+ * evaluated once more: eigenvalues are their Rayleigh quotients v.Cv / v.v, residuals [k] the absolute norms |C v_c - lambda_c v_c|,
+ * converged = 1 iff every residual is <= tol lambda_1.  Running out of iterations is a result (converged = 0), no error.
+ * Rank: a direction of the block whose Gram eigenvalue is not above D 2^-44 times the largest is dropped (its column is
+ * zero from then on); this is where a block wider than the rank of C (at most min(D, n_seqs - 1)), or C = 0, ends up.  A
+ * component beyond that numerical rank -- one whose direction was dropped, or whose Rayleigh quotient is not above
+ * D 2^-52 total_variance -- is returned as a unit vector orthogonal to the others with eigenvalue 0 and residual 0.
+ * Every float64 sum has one order, fixed by constants of the library (256 sequences per serial slice sum, slices
+ * ascending; 32 feature rows per serial chunk sum, chunks ascending): no output bit depends on the launch plan.
+ * PLM_PCA_PLAN forces the plan (measurements and tests): a comma-separated list of g<int> (workgroups per site of the
+ * Phi^T kernel, 1..65535), s<int> (sequences per workgroup of the Phi V kernel, 1..1048576), r<int> (32-row chunks per
+ * workgroup of the b x b products and of the rotation, 1..65535).
+ * plm_pca_fit: scores [n_seqs][k] may be NULL, as may total_variance, total, iterations, converged; where given, scores
+ *   equals plm_pca_project of the same rows through the returned mean and components, bit for bit.
+ * plm_pca_fit_cb: the same with a callback, called once per iteration after its synchronisation with the iteration's
+ *   number and the largest relative residual seen (infinity at the first); a non-zero return stops the loop: the outputs
+ *   describe the vectors reached, converged = 0 and *status = PLM_STATUS_INTERRUPTED (otherwise _CONVERGED / _MAXITER).
+ * plm_pca_project: any n sequences through a given mean [L][q] and components [k][L][q].
+ * PLM_EINVAL (with a message, before the device is looked at): NULL inputs; n_seqs, n < 1; n_sites < 1 (or > 65535); q
+ * outside 2..32; a state outside 0..q-1; k < 1, k > D or k > 64; oversample < 0; a weight that is negative or not finite;
+ * W = 0; tol <= 0; max_iter < 1; skip_state outside -1..q-1; a mean or component that is not finite (plm_pca_project); a
+ * malformed PLM_PCA_PLAN.  PLM_ENOMEM before any allocation when the image, U, the blocks and the slice sums do not fit. */
+typedef struct {
+    int32_t n_components;   /* k >= 1 */
+    int32_t oversample;     /* >= 0; default 8 */
+    int32_t max_iter;       /* >= 1 */
+    int32_t skip_state;     /* -1..q-1 */
+    double  tol;            /* > 0 */
+    uint64_t seed;
+} plm_pca_opts;
+typedef int (*plm_pca_cb)(int32_t iteration, double max_relative_residual, void *user);
+int plm_pca_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
+                const plm_pca_opts *opts, double *mean, double *components, double *eigenvalues, double *residuals,
+                double *total_variance, uint64_t *total, int32_t *iterations, int32_t *converged, double *scores,
+                int device, void *stream);
+int plm_pca_fit_cb(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
+                   const plm_pca_opts *opts, double *mean, double *components, double *eigenvalues, double *residuals,
+                   double *total_variance, uint64_t *total, int32_t *iterations, int32_t *converged, double *scores,
+                   int device, void *stream, plm_pca_cb cb, void *user, int32_t *status);
+int plm_pca_project(const int8_t *seqs, int32_t n, int32_t n_sites, int32_t n_states, const double *mean,
+                    const double *components, int32_t k, int32_t skip_state, double *scores, int device, void *stream);
+
 /* ---- residue distance maps of structures, and their minimum over many chains -----------------------------------------
  * The arithmetic of the reference's compare stage (_distances, compare/distances.py:24-88, and the minimum that
  * DistanceMap.aggregate takes over a stack of maps), all in float64.  For a residue pair (i, j):
