@@ -12,11 +12,10 @@
 #include "plm_gibbs_device.h"
 #include "plm_host_util.h"
 #include "plm_internal.h"
-#include "plm_lbfgs.h"
+#include "plm_lbfgs_driver.h"
 
 #include <math.h>
 #include <stdlib.h>
-#include <chrono>
 #include <cmath>
 #include <type_traits>
 
@@ -501,7 +500,86 @@ int ar_check_data(const int8_t *msa, const float *weights, int n, int L, int q, 
     return PLM_OK;
 }
 
-double ar_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// ArEval as lbfgs_minimize (plm_lbfgs_driver.h) sees it: L-BFGS over float32 parameters with the float64 evaluation
+// above, in one arithmetic -- no variable projection, no straddled pairs, no H0 diagonal, no debug output.  The gradient
+// is rounded to float32 once, where it enters the history; f, g.d of a trial and of the start of a search, and the norms
+// of the stop rule are the float64 sums of k_ar_sums.  One host synchronisation per evaluation.
+struct ArProblem {
+    enum { SL_EVAL = 0, SL_DG0 = 8, SL_EX = 12, SL_MD = 16, SL_COUNT = 16 + 3 * PLM_MAX_BASIS + 1 };
+    static constexpr bool vp = false, debug = false;
+    ArEval &ev;
+    const hipStream_t st;
+    const int m;
+    const double eps;
+    const int64_t nc = ev.n_can, n4 = (nc + 3) / 4 * 4;
+    float *x = nullptr, *xp = nullptr, *g = nullptr, *gp = nullptr, *xa = nullptr, *ga = nullptr, *dir = nullptr, *S = nullptr;
+    double *g64 = nullptr, *g64p = nullptr, *scal = nullptr, *scratch = nullptr, *h_scal = nullptr;
+    int n_evals = 0;
+    double gg = 0, hh = 0, xx = 0;      // float64 g.g, x.x over the fields, x.x at the last accepted point
+
+    // F, its gradient (g64 and, rounded, g) at x; with a direction also g.d
+    int evaluate(const float *direction) {
+        PLM_TRY(ev.enqueue(st, x, g64, scal + SL_EVAL, direction));
+        hipLaunchKernelGGL(k_ar_round, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g64, nc, n4, g);
+        PLM_HIP(hipGetLastError());
+        n_evals++;
+        return PLM_OK;
+    }
+    int fetch() {
+        PLM_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * SL_COUNT, hipMemcpyDeviceToHost, st));
+        PLM_HIP(hipStreamSynchronize(st));
+        return PLM_OK;
+    }
+    int start(LbfgsHistory &hist, LbfgsOutcome *out) {
+        PLM_TRY(evaluate(nullptr));
+        PLM_TRY(fetch());
+        ev.objective(h_scal + SL_EVAL, &out->fx, &out->nll);
+        if (!std::isfinite(out->fx)) return plm_fail(PLM_ENUMERIC, "plm_ar_fit: the objective is not finite at the start point");
+        out->cond = read_norms();
+        first_step(hist);
+        return PLM_OK;
+    }
+    double read_norms() {      // of the evaluation just fetched; returns |g| / max(1, |x|)
+        gg = h_scal[SL_EVAL + 3], hh = h_scal[SL_EVAL + 1], xx = hh + h_scal[SL_EVAL + 2];
+        return std::sqrt(gg) / std::max(1.0, std::sqrt(xx));
+    }
+    LbfgsVectors vectors() const {
+        return {x, g, xp, gp, xa, ga, dir, S, S + (size_t)m * n4, n4, 0, nullptr, scratch, scal + SL_MD, scal + SL_EX,
+                h_scal + SL_MD, st};
+    }
+    // the history's g.g is the float32 gradient's: a steepest-descent step starts from the float64 one
+    double first_step(LbfgsHistory &hist) const {
+        hist.gDg = hist.gg = gg;
+        return 1.0 / std::sqrt(gg);
+    }
+    void swap_points() {
+        std::swap(x, xp);
+        std::swap(g, gp);
+        std::swap(g64, g64p);
+    }
+    // g.d at the point the search starts from, from its float64 gradient; it comes back with the first trial
+    int begin_search() {
+        PLM_HIP(ev.sums(st, xp, g64p, dir, scal + SL_DG0));
+        return PLM_OK;
+    }
+    template <class Pass> int evaluate_trial(int, Pass &&gram_pass) {
+        PLM_TRY(evaluate(dir));
+        PLM_HIP(gram_pass());
+        return fetch();
+    }
+    double search_dg0(double) const { return h_scal[SL_DG0 + 3]; }
+    void trial_values(double *fx, double *nll, double *dg) const {
+        ev.objective(h_scal + SL_EVAL, fx, nll);
+        *dg = h_scal[SL_EVAL + 4];
+    }
+    template <class P> int after_search(int, const MtSearch &, double, double, int, P &&, LbfgsOutcome *, bool *) { return PLM_OK; }
+    void accepted_norms(const LbfgsHistory &, double *cond, double *xx_out, double *hh_out) {
+        *cond = read_norms();
+        *xx_out = xx, *hh_out = hh;
+    }
+    int converged(double *cond, bool *done) const { *done = *cond <= eps; return PLM_OK; }
+    int anchor_buffers() const { return PLM_OK; }      // allocated with the rest
+};
 
 }  // namespace
 
@@ -646,11 +724,8 @@ int plm_ar_eval(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t
     return PLM_OK;
 }
 
-// L-BFGS over float32 parameters with the float64 evaluation above: MtSearch and LbfgsHistory of plm_lbfgs.h as
-// plm_ctx_optimize drives them (coefficient-space two-loop recursion, the pair of a trial formed with its Gram rows in
-// the pass that follows its evaluation), with one arithmetic: no variable projection, no straddled pairs.  The gradient
-// is rounded to float32 once, where it enters the history; f, g.d of a trial and of the start of a search, and the norms
-// of the stop rule are the float64 sums of k_ar_sums.  One host synchronisation per evaluation.
+// The L-BFGS fit: the checks and the buffers of an ArProblem, then lbfgs_minimize (plm_lbfgs_driver.h) -- the iteration
+// that plm_ctx_optimize runs as well.
 int plm_ar_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states,
                const plm_ar_fit_opts *opts, const float *x_start, plm_iter_cb cb, void *user, int device, void *stream,
                float *x_out, plm_ar_fit_result *result) {
@@ -664,150 +739,38 @@ int plm_ar_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t 
         return plm_fail(PLM_EINVAL, "plm_ar_fit: epsilon must be finite and > 0 (got %g)", opts->epsilon);
     if (opts->lbfgs_m < 1 || opts->lbfgs_m > 20) return plm_fail(PLM_EINVAL, "plm_ar_fit: lbfgs_m must be 1..20 (got %d)", opts->lbfgs_m);
     PLM_TRY(plm_check_device(device));
-    const double t0 = ar_now();
+    const double t0 = lbfgs_now();
     const int m = opts->lbfgs_m;
-    const double eps = opts->epsilon;
     ArEval ev(L, q, n, true);
     ev.neff = neff, ev.lambda_h = opts->lambda_h, ev.lambda_j = opts->lambda_j;
-    const int64_t nc = ev.n_can, n4 = (nc + 3) / 4 * 4;
-    enum { SL_EVAL = 0, SL_DG0 = 8, SL_EX = 12, SL_MD = 16, SL_COUNT = 16 + 3 * PLM_MAX_BASIS + 1 };
+    ArProblem p{ev, (hipStream_t)stream, m, opts->epsilon};
+    const int64_t nc = p.nc, n4 = p.n4;
     const size_t scratch_n = (size_t)(3 * PLM_MAX_BASIS + 4) * PLM_DOT_BLOCKS;
     PLM_TRY(plm_check_free(ev.bytes() + 4.0 * n4 * (7 + 2 * m) + 16.0 * nc + 8.0 * scratch_n, "plm_ar_fit",
                            ar_table_bytes(L, q)));
-    hipStream_t st = (hipStream_t)stream;
     DeviceBuffers mem;
-    float *x = nullptr, *xp = nullptr, *g = nullptr, *gp = nullptr, *xa = nullptr, *ga = nullptr, *dir = nullptr, *S = nullptr;
-    double *g64 = nullptr, *g64p = nullptr, *scal = nullptr, *scratch = nullptr, *h_scal = nullptr;
-    for (float **v : {&x, &xp, &g, &gp, &xa, &ga, &dir}) PLM_TRY(mem.alloc(v, (size_t)n4));
-    PLM_TRY(mem.alloc(&S, (size_t)2 * m * n4));
-    float *Y = S + (size_t)m * n4;
-    PLM_TRY(mem.alloc(&g64, (size_t)nc));
-    PLM_TRY(mem.alloc(&g64p, (size_t)nc));
-    PLM_TRY(mem.alloc(&scal, (size_t)SL_COUNT));
-    PLM_TRY(mem.alloc(&scratch, scratch_n));
-    PLM_TRY(mem.alloc_pinned(&h_scal, (size_t)SL_COUNT));
+    for (float **v : {&p.x, &p.xp, &p.g, &p.gp, &p.xa, &p.ga, &p.dir}) PLM_TRY(mem.alloc(v, (size_t)n4));
+    PLM_TRY(mem.alloc(&p.S, (size_t)2 * m * n4));
+    PLM_TRY(mem.alloc(&p.g64, (size_t)nc));
+    PLM_TRY(mem.alloc(&p.g64p, (size_t)nc));
+    PLM_TRY(mem.alloc(&p.scal, (size_t)ArProblem::SL_COUNT));
+    PLM_TRY(mem.alloc(&p.scratch, scratch_n));
+    PLM_TRY(mem.alloc_pinned(&p.h_scal, (size_t)ArProblem::SL_COUNT));
     PLM_TRY(ev.alloc(mem));
-    for (float *v : {x, xp, dir}) PLM_HIP(hipMemsetAsync(v, 0, sizeof(float) * n4, st));
-    if (x_start) PLM_HIP(hipMemcpyAsync(x, x_start, sizeof(float) * nc, hipMemcpyHostToDevice, st));
-    PLM_TRY(ev.upload(st, msa, w.data()));
-
-    int n_evals = 0;
-    // F, its gradient (g64 and, rounded, g) at x; with a direction also g.d
-    auto evaluate = [&](const float *direction) -> int {
-        PLM_TRY(ev.enqueue(st, x, g64, scal + SL_EVAL, direction));
-        hipLaunchKernelGGL(k_ar_round, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g64, nc, n4, g);
-        PLM_HIP(hipGetLastError());
-        n_evals++;
-        return PLM_OK;
-    };
-    auto fetch = [&]() -> int {
-        PLM_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * SL_COUNT, hipMemcpyDeviceToHost, st));
-        PLM_HIP(hipStreamSynchronize(st));
-        return PLM_OK;
-    };
-    PLM_TRY(evaluate(nullptr));
-    PLM_TRY(fetch());
-    double fx, nll;
-    ev.objective(h_scal + SL_EVAL, &fx, &nll);
-    if (!std::isfinite(fx)) return plm_fail(PLM_ENUMERIC, "plm_ar_fit: the objective is not finite at the start point");
-    double gg = h_scal[SL_EVAL + 3], hh = h_scal[SL_EVAL + 1], xx = hh + h_scal[SL_EVAL + 2];
-    auto cond_of = [&]() { return std::sqrt(gg) / std::max(1.0, std::sqrt(xx)); };
-    LbfgsHistory hist(m);
-    hist.gDg = hist.gg = gg;
-    int k = 0, status = PLM_STATUS_CONVERGED, ls_reason = 0, restarts = 0;
-    if (cond_of() > eps) {
-        double step = 1.0 / std::sqrt(gg);
-        for (k = 1;; k++) {
-            double cg, dg_gram;
-            hist.coefficients(&cg, &dg_gram);
-            if (!(dg_gram < 0)) { status = PLM_STATUS_LINESEARCH; ls_reason = 10; k--; break; }
-            PlmVecList B;
-            PlmCoefList C;
-            const int first_weighted =
-                lbfgs_direction_basis(S, Y, g, n4, m, hist.stored, hist.end, hist.cs.data(), hist.cy.data(), cg, &B, &C);
-            // the direction and the first trial point, which lands where the trial points are built after the swap
-            const float stp0 = (float)std::max(MtSearch::stpmin, std::min(MtSearch::stpmax, step));
-            PLM_HIP(plm_launch_multiaxpy_trial(dir, B, C, n4, nullptr, first_weighted, x, stp0, xp, st));
-            std::swap(x, xp);
-            std::swap(g, gp);
-            std::swap(g64, g64p);
-            // g.d at the point the search starts from, from its float64 gradient; it comes back with the first trial
-            PLM_HIP(ev.sums(st, xp, g64p, dir, scal + SL_DG0));
-            const double finit = fx, nllinit = nll;
-            float *s_new = S + (size_t)hist.end * n4, *y_new = Y + (size_t)hist.end * n4;
-            const int nst = hist.nst();
-            unsigned long long wb;
-            unsigned wq;
-            lbfgs_gram_basis(S, Y, g, n4, nst, &B, &wb, &wq);
-            MtSearch ls;
-            int lsrc = 0;
-            bool first = true;
-            do {
-                if (!first) {
-                    const double stp = ls.next();
-                    PLM_HIP(plm_launch_lincomb(x, 1.f, xp, (float)stp, dir, n4, st));
-                }
-                PLM_TRY(evaluate(dir));
-                // speculate that the trial is accepted: its pair goes to slot `end` with its Gram rows, in the same fetch
-                PLM_HIP(plm_launch_sy_multidot(s_new, y_new, x, hist.anchored ? xa : xp, g, hist.anchored ? ga : gp, dir, B, n4,
-                                               0, scratch, scal + SL_MD, scal + SL_EX, nullptr, wq, wb, st));
-                PLM_TRY(fetch());
-                if (first) {
-                    const double dginit = h_scal[SL_DG0 + 3];
-                    if (!(dginit < 0)) { lsrc = -10; break; }
-                    ls.start(finit, dginit, step);
-                    ls.next();
-                    first = false;
-                }
-                ev.objective(h_scal + SL_EVAL, &fx, &nll);
-                lsrc = ls.feed(fx, h_scal[SL_EVAL + 4]);
-            } while (lsrc == 0);
-            if (lsrc < 0) {
-                // the last accepted point is still in (xp, gp, g64p): make it current again
-                std::swap(x, xp);
-                std::swap(g, gp);
-                std::swap(g64, g64p);
-                fx = finit;
-                nll = nllinit;
-                k--;
-                if (hist.stored > 0 && restarts < 2) {      // a stale model: drop the history, retry from steepest descent
-                    restarts++;
-                    hist.reset();
-                    hist.gDg = hist.gg = gg;
-                    step = 1.0 / std::sqrt(gg);
-                    continue;
-                }
-                status = PLM_STATUS_LINESEARCH;
-                ls_reason = -lsrc;
-                break;
-            }
-            restarts = 0;
-            const double *md = h_scal + SL_MD;
-            const int nbv = B.n;
-            hist.absorb(md, nbv, nst);
-            gg = h_scal[SL_EVAL + 3], hh = h_scal[SL_EVAL + 1], xx = hh + h_scal[SL_EVAL + 2];
-            if (cb && cb(k, ar_now() - t0, cond_of(), fx, nll, std::sqrt(hh), std::sqrt(std::max(0.0, xx - hh)), user) != 0) {
-                status = PLM_STATUS_INTERRUPTED;
-                break;
-            }
-            if (cond_of() <= eps) { status = PLM_STATUS_CONVERGED; break; }
-            if (opts->max_iter > 0 && k >= opts->max_iter) { status = PLM_STATUS_MAXITER; break; }
-            if (hist.admit(md, nbv, nst, false, false, false).copy_anchor) {
-                PLM_HIP(hipMemcpyAsync(xa, xp, sizeof(float) * n4, hipMemcpyDeviceToDevice, st));
-                PLM_HIP(hipMemcpyAsync(ga, gp, sizeof(float) * n4, hipMemcpyDeviceToDevice, st));
-            }
-            step = 1.0;
-        }
-    }
-    PLM_HIP(hipMemcpyAsync(x_out, x, sizeof(float) * nc, hipMemcpyDeviceToHost, st));
-    PLM_HIP(hipStreamSynchronize(st));
-    result->status = status;
-    result->iterations = k;
-    result->evaluations = n_evals;
-    result->ls_reason = ls_reason;
-    result->fx = fx;
-    result->nll = nll;
-    result->gnorm = std::sqrt(gg);
-    result->xnorm = std::sqrt(xx);
+    for (float *v : {p.x, p.xp, p.dir}) PLM_HIP(hipMemsetAsync(v, 0, sizeof(float) * n4, p.st));
+    if (x_start) PLM_HIP(hipMemcpyAsync(p.x, x_start, sizeof(float) * nc, hipMemcpyHostToDevice, p.st));
+    PLM_TRY(ev.upload(p.st, msa, w.data()));
+    LbfgsOutcome o;
+    PLM_TRY(lbfgs_minimize(p, LbfgsLimits{m, opts->epsilon, opts->max_iter, cb, user, t0}, &o));
+    PLM_HIP(hipMemcpyAsync(x_out, p.x, sizeof(float) * nc, hipMemcpyDeviceToHost, p.st));
+    PLM_HIP(hipStreamSynchronize(p.st));
+    result->status = o.status;
+    result->iterations = o.k;
+    result->evaluations = p.n_evals;
+    result->ls_reason = o.ls_reason;
+    result->fx = o.fx;
+    result->nll = o.nll;
+    result->gnorm = std::sqrt(p.gg);
+    result->xnorm = std::sqrt(p.xx);
     return PLM_OK;
 }

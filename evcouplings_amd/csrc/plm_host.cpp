@@ -1,11 +1,10 @@
-// plm_host.cpp -- context, evaluation pipeline, L-BFGS driver and the C ABI of libplm_hip.so
+// plm_host.cpp -- context, evaluation pipeline, the context's side of the L-BFGS iteration (CtxProblem; the iteration
+// itself is lbfgs_minimize of plm_lbfgs_driver.h) and the C ABI of libplm_hip.so
 // (include/plm_hip.h).  Replaces the plmc child process of evcouplings/couplings/tools.py:266.
 // No CPU fallback exists: every entry point needs a gfx950 device and fails with
 // PLM_EDEVICE otherwise.
 #include "../../include/plm_hip.h"
-#include "plm_internal.h"
-#include "plm_host_util.h"
-#include "plm_lbfgs.h"
+#include "plm_lbfgs_driver.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1262,64 +1261,31 @@ static int ctx_build_dinv(plm_ctx_t *c) {
     PLM_HIP(hipStreamSynchronize(c->st));   // fv leaves scope
     return PLM_OK;
 }
-// L-BFGS with a More'-Thuente line search; vectors stay in HBM, only scalars cross PCIe.
-// Defaults follow libLBFGS (m = 6, ftol 1e-4, gtol 0.9, <= 20 trial steps), which plmc bundles
-// [recollection, SURVEY.md App. C.4].  The two-loop recursion (Nocedal 1980) is evaluated in
-// coefficient space ("vector-free" L-BFGS, Chen et al. 2014): every inner product it needs is an
-// entry of the Gram matrix of {s_j, y_j, g}, refreshed by ONE pass over the history per
-// iteration (k_multidot), and the direction is ONE fused linear combination (k_multiaxpy).
-// Two host synchronisations per iteration: after the line-search evaluation and after the pass.
-int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res) {
-    if (!c) return fail(PLM_EINVAL, "NULL ctx");
-    if (!c->have_weights) return fail(PLM_EINVAL, "weights not set");
-    PLM_HIP(hipSetDevice(c->device));
-    const double eps = c->prob.epsilon > 0 ? c->prob.epsilon : 1e-3;
-    const double t0 = now_s();
+// plm_ctx as lbfgs_minimize (plm_lbfgs_driver.h) sees it: everything that is about THIS objective -- its evaluation in
+// two arithmetics, the variable projection with its tolerance and its certificate, the sharded sums.  Only scalars cross
+// PCIe: one host synchronisation per trial.
+extern "C++" {
+namespace {
+struct CtxProblem {
+    // device scalar slots; in sharded-state mode each fetch is preceded by a sum over the shards of
+    // exactly the slots that were just written ([FX..DG] after an evaluation, [XX..MD+..] after the pass)
+    enum { SL_FX = 0, SL_NLL = 1, SL_DG = 2, SL_XX = 3, SL_HH = 4, SL_GH2 = 5, SL_MD = 8 };
+    plm_ctx *const c;
+    const double eps;
+    const int m;
     const PlmDims &d = c->d;
     const int64_t n = d.n_local;
-    const int m = std::min(20, c->prob.lbfgs_m > 0 ? c->prob.lbfgs_m : 6);
-    const int max_iter = c->prob.max_iter;
-    PLM_TRY(ctx_alloc_lbfgs(c, m));
-    float *S = c->hist, *Y = c->hist + (size_t)m * n;
     // H0 = gamma * D^-1 with D the Hessian diagonal of the independent-site model at the start point (closed form
     // from the single-site frequencies).  The recursion only ever needs s.y, s.g and the D^-1-weighted products of
     // {y_j, g}.  Opt-in (PLM_FLAG_PRECOND): measured to need MORE iterations than the scalar H0 at L = 300.
     const bool precond = (c->prob.flags & PLM_FLAG_PRECOND) && !c->h_fi.empty();
-    if (precond) PLM_TRY(ctx_build_dinv(c));
-    const float *dinv = precond ? c->dinv : nullptr;
-    LbfgsHistory hist(m);      // the ring of pairs and the Gram matrix of {s_j, y_j, g} (plm_lbfgs.h)
-    double xx = 0, hh = 0;
-    c->n_evals = 0;
-    // device scalar slots; in sharded-state mode each fetch is preceded by a sum over the shards of
-    // exactly the slots that were just written ([FX..DG] after an evaluation, [XX..MD+..] after the pass)
-    enum { SL_FX = 0, SL_NLL = 1, SL_DG = 2, SL_XX = 3, SL_HH = 4, SL_GH2 = 5, SL_MD = 8 };
-
-    auto norm_dots = [&]() -> int {   // x.x (all) and x.x (fields only)
-        const float *a[1] = {c->x};
-        PLM_TRY(dots(c, 1, a, a, n, SL_XX));
-        PLM_TRY(dots(c, 1, a, a, d.nh_pad_l, SL_HH));
-        return PLM_OK;
-    };
-    // trial != nullptr: the launch also writes the first trial point of the line search, trial = xacc + stp0 * p
-    auto direction = [&](double *dginit, const float *xacc, float stp0, float *trial) -> int {
-        double cg;
-        hist.coefficients(&cg, dginit);
-        PlmVecList B;
-        PlmCoefList C;
-        const int first_weighted =
-            lbfgs_direction_basis(S, Y, c->g, n, m, hist.stored, hist.end, hist.cs.data(), hist.cy.data(), cg, &B, &C);
-        if (trial) PLM_HIP(plm_launch_multiaxpy_trial(c->dir, B, C, n, dinv, first_weighted, xacc, stp0, trial, c->st));
-        else PLM_HIP(plm_launch_multiaxpy(c->dir, B, C, n, dinv, first_weighted, c->st));
-        return PLM_OK;
-    };
-
     // variable projection: the fields are solved exactly for every trial couplings (the chain of ctx_eval_vp_enqueue);
     // L-BFGS then only sees the couplings (field part of g is zero, field part of s = the change of the optimal fields)
-    const bool vp = vp_enabled(c);
-    if (vp) PLM_TRY(vp_alloc(c));
-    c->stat_field_ms = c->stat_passes = c->stat_fwd_ms = c->stat_bwd_ms = 0;
-    c->stat_field_evals = c->stat_chain_short = c->stat_gemm_evals = 0;
-    double gh2 = 0;                          // |grad_h|^2 left by the field solver at the current point
+    const bool vp = vp_enabled(c), debug = c->opt.debug;
+    const float *dinv = nullptr;
+    LbfgsHistory *hist = nullptr;
+    double xx = 0;                           // x.x at the last accepted point
+    double gh2 = 0, gh2_trial = 0;           // |grad_h|^2 left by the field solver at the current point / at the trial
     // field-solver tolerance: a fraction of what the stop rule allows the whole gradient, and never below what the
     // solver can reach.  The fields themselves are iterated in f64 (k_hsolve); what is left is the random f32
     // rounding of the stored potentials and of the softmax, ~1e-7 per (sequence, site) term, i.e.
@@ -1338,12 +1304,10 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // The floor itself is not part of the tolerance any more (round 5): the chain ends ON the pass that meets the
     // tolerance, so a tolerance of the floor's size would leave |g_h| at that size -- 2e-6 |x| on a small problem, the
     // whole of a tight stop rule; the chain goes below the floor while a pass still gains a factor 2 (k_vp_check).
-    const double vp_rel = c->opt.vp_rel;
-    c->vp_floor2 = ctx_vp_floor2(c);
-    auto vp_tol2 = [&](double xnorm2) {
-        const double t = std::max(0.1 * eps * std::max(1.0, std::sqrt(xnorm2)), vp_rel * std::sqrt(hist.gg));
+    double vp_tol2(double xnorm2) const {
+        const double t = std::max(0.1 * eps * std::max(1.0, std::sqrt(xnorm2)), c->opt.vp_rel * std::sqrt(hist->gg));
         return t * t;
-    };
+    }
     // Forward-GEMM mode.  The plain instantiation's f32 accumulation leaves an error of ~3e-11 N L |x| in the gradient
     // (4.5e-4 |x| at the headline, 1e-3 |x| at N = 100 000 -- the size of the default stop rule).
     // Far from the optimum that is irrelevant; the last iterations run the accurate instantiation (f64 outer sums), so the
@@ -1352,20 +1316,20 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     const double fwd_noise = 3e-11 * (double)d.N * (double)d.L;
     const double acc_thr = std::max(3.0 * eps, c->opt.acc_factor * fwd_noise);
     // (a problem whose plain-kernel error is below a twentieth of the stop rule never needs the switch)
-    auto want_accurate = [&](double cond) {
+    bool want_accurate(double cond) const {
         return c->opt.fwd_mode == 1 || (c->opt.fwd_mode != 0 && fwd_noise > 0.05 * eps && cond < acc_thr);
-    };
-    // objective and gradient at the start point -- unless this context still holds them (a resumed fit)
-    const bool resume = c->eval_valid && c->eval_vp == vp;
-    ctx_set_accurate(c, c->opt.fwd_mode == 1 || (c->opt.fwd_mode != 0 && resume && c->eval_accurate));
-    auto start_eval = [&](bool have) -> int {
+    }
+    // objective and gradient at c->x (have: this context still holds them), with the norms the first direction needs
+    int start_eval(bool have) {
         const double tol2 = vp_tol2((double)d.L);
         auto fetch = [&]() -> int {      // the norms the first direction needs, with the evaluation's scalars
             PlmVecList Qg, Bg;
             Qg.n = 1; Qg.v[0] = c->g;
             Bg.n = 2; Bg.v[0] = c->g; Bg.v[1] = c->g;
             PLM_HIP(plm_launch_multidot(Qg, Bg, n, c->dot_scratch, c->scal + SL_MD, dinv, 1u, 1ull, c->st));   // gDg, gg
-            PLM_TRY(norm_dots());
+            const float *a[1] = {c->x};      // x.x (all) and x.x (fields only)
+            PLM_TRY(dots(c, 1, a, a, n, SL_XX));
+            PLM_TRY(dots(c, 1, a, a, d.nh_pad_l, SL_HH));
             PLM_TRY(ctx_allreduce_scalars(c, have ? SL_DG : 0, (have ? 8 - SL_DG : 8) + 2));
             PLM_TRY(fetch_scalars(c, 0, 10));
             return PLM_OK;
@@ -1376,22 +1340,10 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
             if (!have) PLM_TRY(ctx_eval_enqueue(c));
             PLM_TRY(fetch());
         }
-        hist.gDg = c->h_scal[SL_MD];
-        hist.gg = c->h_scal[SL_MD + 1];
+        hist->gDg = c->h_scal[SL_MD];
+        hist->gg = c->h_scal[SL_MD + 1];
         xx = c->h_scal[SL_XX];
-        hh = c->h_scal[SL_HH];
         return PLM_OK;
-    };
-    PLM_TRY(start_eval(resume));
-    if (resume) gh2 = c->last_gh2;
-    double fx = resume ? c->last_fx : c->h_scal[SL_FX], nll = resume ? c->last_nll : c->h_scal[SL_NLL];
-    c->eval_valid = false;
-    if (!std::isfinite(fx)) return fail(PLM_ENUMERIC, "objective is not finite at the start point");
-    if (!c->fwd_accurate && want_accurate(std::sqrt(hist.gg + gh2) / std::max(1.0, std::sqrt(xx)))) {
-        ctx_set_accurate(c, true);   // a start point this close to the optimum: its gradient decides the stop rule
-        PLM_TRY(start_eval(false));
-        fx = c->h_scal[SL_FX];
-        nll = c->h_scal[SL_NLL];
     }
     // Certificate of the point that SHIPS.  The field solver iterates the fields in f64; the parameter vector (and the
     // .model file) holds them rounded to f32.  A field off by 2^-25 |h| changes the gradient by (N-proportional
@@ -1400,7 +1352,7 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
     // gradient -- fields included -- is evaluated once at the rounded point (the stored potentials are reused: residual
     // pass, backward GEMM, assemble into the free direction vector); the fit ends only if THAT meets the rule, otherwise
     // it goes on with a target lowered by what the rounding costs.
-    auto shipped_cond = [&](double *out) -> int {
+    int shipped_cond(double *out) {
         PLM_HIP(plm_launch_h64_init(d, c->x, c->h64, c->st));
         PLM_HIP(plm_launch_hpass(d, c->hj, c->msa_rm, c->w, c->h64, 1, 0, c->fwd_accurate, c->Rt, c->fx_part, nullptr, nullptr,
                                  nullptr, nullptr, PLM_VP_ALWAYS, c->st));
@@ -1411,192 +1363,176 @@ int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res
         PLM_TRY(fetch_scalars(c, SL_DG, 1));
         *out = std::sqrt(c->h_scal[SL_DG]) / std::max(1.0, std::sqrt(xx));
         return PLM_OK;
-    };
+    }
     double eps_eff = eps;      // target of the reduced gradient: the stop rule minus what the f32 rounding of the fields costs
     double rounding_note = 0;  // > 0: the rule was met on the f64-field point only; what rounding the fields to f32 adds
     int n_cert = 0;
-    int k = 0, status = PLM_STATUS_CONVERGED, ls_reason = 0, restarts = 0;
-    double last_cond = std::sqrt(hist.gg + gh2) / std::max(1.0, std::sqrt(xx));   // |g|/max(1,|x|) at the last accepted point
-    // (a resumed fit as well -- its previous run certified the point for ITS epsilon -- when the potentials of the
-    // point are still there)
-    if (last_cond <= eps && vp && (!resume || c->hj_at_x)) {   // a start point that meets the rule must meet it as it ships, too
+
+    int start(LbfgsHistory &h, LbfgsOutcome *out) {
+        hist = &h;
+        PLM_TRY(ctx_alloc_lbfgs(c, m));
+        if (precond) PLM_TRY(ctx_build_dinv(c));
+        dinv = precond ? c->dinv : nullptr;
+        c->n_evals = 0;
+        if (vp) PLM_TRY(vp_alloc(c));
+        c->stat_field_ms = c->stat_passes = c->stat_fwd_ms = c->stat_bwd_ms = 0;
+        c->stat_field_evals = c->stat_chain_short = c->stat_gemm_evals = 0;
+        c->vp_floor2 = ctx_vp_floor2(c);
+        // objective and gradient at the start point -- unless this context still holds them (a resumed fit)
+        const bool resume = c->eval_valid && c->eval_vp == vp;
+        ctx_set_accurate(c, c->opt.fwd_mode == 1 || (c->opt.fwd_mode != 0 && resume && c->eval_accurate));
+        PLM_TRY(start_eval(resume));
+        if (resume) gh2 = c->last_gh2;
+        out->fx = resume ? c->last_fx : c->h_scal[SL_FX];
+        out->nll = resume ? c->last_nll : c->h_scal[SL_NLL];
+        c->eval_valid = false;
+        if (!std::isfinite(out->fx)) return fail(PLM_ENUMERIC, "objective is not finite at the start point");
+        if (!c->fwd_accurate && want_accurate(std::sqrt(h.gg + gh2) / std::max(1.0, std::sqrt(xx)))) {
+            ctx_set_accurate(c, true);   // a start point this close to the optimum: its gradient decides the stop rule
+            PLM_TRY(start_eval(false));
+            out->fx = c->h_scal[SL_FX];
+            out->nll = c->h_scal[SL_NLL];
+        }
+        out->cond = std::sqrt(h.gg + gh2) / std::max(1.0, std::sqrt(xx));   // |g|/max(1,|x|) at the last accepted point
+        // (a resumed fit as well -- its previous run certified the point for ITS epsilon -- when the potentials of the
+        // point are still there)
+        if (out->cond <= eps && vp && (!resume || c->hj_at_x)) {   // a start point that meets the rule must meet it as it ships, too
+            double cj = 0;
+            PLM_TRY(shipped_cond(&cj));
+            const double r2 = std::max(0.0, cj * cj - out->cond * out->cond);
+            if (cj > eps && r2 >= 0.75 * eps * eps) rounding_note = std::sqrt(r2);       // not representable in float32 fields
+            else if (cj > eps) { eps_eff = std::sqrt(eps * eps - r2); out->cond = cj; }   // go on until the shipped point meets it
+        }
+        return PLM_OK;
+    }
+    LbfgsVectors vectors() const {
+        return {c->x, c->g, c->xp, c->gp, c->xa, c->ga, c->dir, c->hist, c->hist + (size_t)m * n, n, d.nh_pad_l, dinv,
+                c->dot_scratch, c->scal + SL_MD, c->scal + SL_DG, c->h_scal + SL_MD, c->st};
+    }
+    // first step: unit displacement along the plain gradient; the D^-1-scaled direction is Newton-like for the
+    // diagonal part of the Hessian, so it starts from min(1, that)
+    double first_step(const LbfgsHistory &h) const {
+        return precond ? std::min(1.0, 1.0 / std::sqrt(h.gDg)) : 1.0 / std::sqrt(h.gg);
+    }
+    void swap_points() {
+        std::swap(c->x, c->xp);
+        std::swap(c->g, c->gp);
+    }
+    int begin_search() { gh2_trial = 0; return PLM_OK; }
+    // objective + gradient at the trial point c->x, and with it everything the NEXT direction needs
+    template <class Pass> int evaluate_trial(int nbv, Pass &&gram_pass) {
+        const double tol2 = vp_tol2(xx);
+        if (!vp) PLM_TRY(ctx_eval_enqueue(c));
+        else PLM_TRY(ctx_eval_vp_enqueue(c, tol2));
+        for (;;) {
+            // (round 6: pair, Gram rows, g.p, x.x and the fields' x.x in ONE pass over the vectors; sharded, one
+            // all-reduce per trial as well)
+            PLM_HIP(gram_pass());
+            PLM_TRY(ctx_allreduce_scalars(c, SL_FX, SL_MD + 3 * nbv + 1 - SL_FX));
+            PLM_TRY(fetch_scalars(c, SL_FX, SL_MD + 3 * nbv + 1 - SL_FX));
+            bool again = false;      // the field solver's chain ran out of positions: more was enqueued (rare)
+            if (vp) PLM_TRY(ctx_eval_vp_finish(c, tol2, &again, &gh2_trial));
+            if (!again) break;
+        }
+        return PLM_OK;
+    }
+    double search_dg0(double dg_gram) const { return dg_gram; }   // the Gram value: the gradient has one precision
+    void trial_values(double *fx, double *nll, double *dg) const {
+        *fx = c->h_scal[SL_FX];
+        *nll = c->h_scal[SL_NLL];
+        *dg = c->h_scal[SL_DG];
+    }
+    // gg_trial: g.g of the accepted trial as its Gram pass saw it
+    template <class Pass>
+    int after_search(int k, const MtSearch &ls, double dg, double gg_trial, int nbv, Pass &&gram_pass, LbfgsOutcome *out,
+                     bool *straddle) {
+        if (debug)
+            fprintf(stderr, "[plm] it %d: %d trial(s), step %.4e (first %.4e), f - f0 = %.6e, dg0 = %.4e, dg = %.4e%s\n", k, ls.count, ls.stp,
+                    ls.trace[0][0], out->fx - ls.finit, ls.dginit, dg, c->fwd_accurate ? " [accurate]" : "");
+        if (!c->fwd_accurate && want_accurate(std::sqrt(gg_trial + gh2_trial) / std::max(1.0, std::sqrt(c->h_scal[SL_XX])))) {
+            ctx_set_accurate(c, true);      // from here on: the accurate arithmetic, starting with this very point
+            *straddle = true;
+            PLM_TRY(evaluate_trial(nbv, gram_pass));
+            out->fx = c->h_scal[SL_FX];
+            out->nll = c->h_scal[SL_NLL];
+            if (!std::isfinite(out->fx)) return fail(PLM_ENUMERIC, "objective is not finite after the switch of the forward GEMM");
+        }
+        return PLM_OK;
+    }
+    void accepted_norms(const LbfgsHistory &h, double *cond, double *xx_out, double *hh_out) {
+        *xx_out = xx = c->h_scal[SL_XX];
+        *hh_out = c->h_scal[SL_HH];
+        gh2 = gh2_trial;
+        const double xnorm = std::sqrt(xx), gnorm = std::sqrt(h.gg + gh2);
+        *cond = gnorm / std::max(1.0, xnorm);
+    }
+    int converged(double *cond, bool *done) {
+        if (!(*cond <= eps_eff)) return PLM_OK;
+        *done = true;
+        if (!vp) return PLM_OK;
         double cj = 0;
         PLM_TRY(shipped_cond(&cj));
-        const double r2 = std::max(0.0, cj * cj - last_cond * last_cond);
-        if (cj > eps && r2 >= 0.75 * eps * eps) rounding_note = std::sqrt(r2);       // not representable in float32 fields
-        else if (cj > eps) { eps_eff = std::sqrt(eps * eps - r2); last_cond = cj; }   // go on until the shipped point meets it
-    }
-    if (last_cond > eps) {
-        // first step: unit displacement along the plain gradient; the D^-1-scaled direction is Newton-like for the
-        // diagonal part of the Hessian, so it starts from min(1, that)
-        auto first_step = [&]() { return precond ? std::min(1.0, 1.0 / std::sqrt(hist.gDg)) : 1.0 / std::sqrt(hist.gg); };
-        double step = first_step();
-        for (k = 1;; k++) {
-            double dginit;
-            // the direction and, in the same pass, the first trial point x + stp0 p -- written where the trial points are
-            // built after the swap below (today's xp: the point before the accepted one, not needed any more unless it is
-            // still the anchor of the next pair, which lives in its own buffers then)
-            const float stp0 = (float)std::max(MtSearch::stpmin, std::min(MtSearch::stpmax, step));
-            PLM_TRY(direction(&dginit, c->x, stp0, c->xp));
-            if (!(dginit < 0)) { status = PLM_STATUS_LINESEARCH; ls_reason = 10; k--; break; }
-            // the accepted point moves to (xp, gp); trial points are built in (x, g)
-            std::swap(c->x, c->xp);
-            std::swap(c->g, c->gp);
-            const double finit = fx, nllinit = nll;
-            // the new pair goes into slot `end`; queries and basis of the Gram pass (rows for s, y, g)
-            float *s_new = S + (size_t)hist.end * n, *y_new = Y + (size_t)hist.end * n;
-            const int nst = hist.nst();
-            PlmVecList B;
-            unsigned long long wb;                        // basis vectors that enter products in the H0 metric: Y, g
-            unsigned wq;                                  // queries y_new and g
-            lbfgs_gram_basis(S, Y, c->g, n, nst, &B, &wb, &wq);      // c->g: the buffer the trial gradients land in
-            double gh2_trial = 0;
-            // objective + gradient at the trial point c->x, and with it everything the NEXT direction needs
-            auto evaluate_trial = [&]() -> int {
-                const double tol2 = vp_tol2(xx);
-                if (!vp) PLM_TRY(ctx_eval_enqueue(c));
-                else PLM_TRY(ctx_eval_vp_enqueue(c, tol2));
-              for (;;) {
-                // Speculate that this trial point is accepted (it is, 97 % of the time): form its (s, y) pair
-                // in slot `end` -- the slot the next pair goes to anyway; a rejected trial is simply
-                // overwritten by the next one -- and run the Gram pass now, so that ONE host
-                // synchronisation (and, sharded, one all-reduce) per trial brings back f, the directional
-                // derivative and everything the next direction needs.
-                // (round 6: pair, Gram rows, g.p, x.x and the fields' x.x in ONE pass over the vectors)
-                PLM_HIP(plm_launch_sy_multidot(s_new, y_new, c->x, hist.anchored ? c->xa : c->xp, c->g, hist.anchored ? c->ga : c->gp,
-                                               c->dir, B, n, d.nh_pad_l, c->dot_scratch, c->scal + SL_MD, c->scal + SL_DG, dinv,
-                                               wq, wb, c->st));
-                PLM_TRY(ctx_allreduce_scalars(c, SL_FX, SL_MD + 3 * B.n + 1 - SL_FX));
-                PLM_TRY(fetch_scalars(c, SL_FX, SL_MD + 3 * B.n + 1 - SL_FX));
-                bool again = false;      // the field solver's chain ran out of positions: more was enqueued (rare)
-                if (vp) PLM_TRY(ctx_eval_vp_finish(c, tol2, &again, &gh2_trial));
-                if (!again) break;
-              }
-                return PLM_OK;
-            };
-            MtSearch ls;
-            ls.start(finit, dginit, step);
-            int lsrc;
-            do {
-                const double stp = ls.next();
-                if (!(ls.count == 0 && (float)stp == stp0))      // the first trial point came with the direction
-                    PLM_HIP(plm_launch_lincomb(c->x, 1.f, c->xp, (float)stp, c->dir, n, c->st));
-                PLM_TRY(evaluate_trial());
-                double dg = c->h_scal[SL_DG];
-                fx = c->h_scal[SL_FX];
-                nll = c->h_scal[SL_NLL];
-                lsrc = ls.feed(fx, dg);
-            } while (lsrc == 0);
-            if (lsrc < 0 && c->opt.debug) ls.dump_failure(k, lsrc);
-            if (lsrc < 0) {
-                // the last accepted point is still in (xp, gp): make it current again
-                std::swap(c->x, c->xp);
-                std::swap(c->g, c->gp);
-                fx = finit;
-                nll = nllinit;
-                k--;
-                if (hist.stored > 0 && restarts < 2) {
-                    // a stale quasi-Newton model is the usual reason near the f32 floor: drop the history
-                    // and retry once from steepest descent before giving up
-                    restarts++;
-                    hist.reset();
-                    step = first_step();
-                    continue;
-                }
-                status = PLM_STATUS_LINESEARCH;
-                ls_reason = -lsrc;
-                break;
-            }
-            restarts = 0;
-            if (c->opt.debug)
-                fprintf(stderr, "[plm] it %d: %d trial(s), step %.4e (first %.4e), f - f0 = %.6e, dg0 = %.4e, dg = %.4e%s\n", k, ls.count, ls.stp,
-                        ls.trace[0][0], fx - finit, dginit, c->h_scal[SL_DG], c->fwd_accurate ? " [accurate]" : "");
-            step = ls.stp;
-            // the pair of the accepted point already sits in slot `end` and its Gram rows in h_scal (see above)
-            const double *md = c->h_scal + SL_MD;
-            const int nbv = B.n;
-            bool straddle = false;              // this step's pair would difference gradients of two arithmetics
-            if (!c->fwd_accurate &&
-                want_accurate(std::sqrt(md[2 * nbv + 2 * nst + 1] + gh2_trial) / std::max(1.0, std::sqrt(c->h_scal[SL_XX])))) {
-                ctx_set_accurate(c, true);      // from here on: the accurate arithmetic, starting with this very point
-                straddle = true;
-                PLM_TRY(evaluate_trial());
-                fx = c->h_scal[SL_FX];
-                nll = c->h_scal[SL_NLL];
-                if (!std::isfinite(fx)) return fail(PLM_ENUMERIC, "objective is not finite after the switch of the forward GEMM");
-            }
-            hist.absorb(md, nbv, nst);
-            xx = c->h_scal[SL_XX];
-            hh = c->h_scal[SL_HH];
-            gh2 = gh2_trial;
-            const double xnorm = std::sqrt(xx), gnorm = std::sqrt(hist.gg + gh2);
-            last_cond = gnorm / std::max(1.0, xnorm);
-            // a non-zero return cancels the fit (a pipeline's SIGTERM / SIGINT handler, evcouplings/utils/pipeline.py:476-545,
-            // raised inside a Python callback): the point reached so far stays in the context
-            if (cb && cb(k, now_s() - t0, last_cond, fx, nll, std::sqrt(hh), std::sqrt(std::max(0.0, xx - hh)), user) != 0) {
-                status = PLM_STATUS_INTERRUPTED;
-                break;
-            }
-            if (last_cond <= eps_eff) {
-                if (!vp) { status = PLM_STATUS_CONVERGED; break; }
-                double cj = 0;
-                PLM_TRY(shipped_cond(&cj));
-                if (!(cj > eps)) { last_cond = cj; status = PLM_STATUS_CONVERGED; break; }
-                const double r2 = std::max(0.0, cj * cj - last_cond * last_cond);     // the rounding's share
-                if (r2 >= 0.75 * eps * eps || ++n_cert > 8) {     // the target would fall below eps / 2
-                    // float32 fields cannot carry this stop rule (a rule far below 1e-3, or a very deep alignment): the
-                    // fit ends by the rule on its own (f64-field) point and says what the rounding adds
-                    status = PLM_STATUS_CONVERGED;
-                    rounding_note = std::sqrt(r2);
-                    break;
-                }
-                eps_eff = std::min(0.9 * eps_eff, std::sqrt(eps * eps - r2));
-            }
-            if (max_iter > 0 && k >= max_iter) { status = PLM_STATUS_MAXITER; break; }
-            // the pair of the accepted step: stored, dropped as a straddle, skipped as noise, or the history restarted
-            if (hist.admit(md, nbv, nst, vp, straddle, c->opt.debug).copy_anchor) {
-                // keep the point the pair started from: (xp, gp) is overwritten by the next swap
-                if (!c->xa) {
-                    PLM_TRY(plm_dalloc(&c->xa, (size_t)n));
-                    PLM_TRY(plm_dalloc(&c->ga, (size_t)n));
-                }
-                PLM_HIP(hipMemcpyAsync(c->xa, c->xp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-                PLM_HIP(hipMemcpyAsync(c->ga, c->gp, sizeof(float) * n, hipMemcpyDeviceToDevice, c->st));
-            }
-            step = 1.0;
-            // (Rounds 4-5 kept a stagnation watch here -- no new best |g|/|x| for 12 iterations next to the stop rule ->
-            // history dropped.  It did not fire in any run since the accurate evaluation took over the last iterations of a
-            // fit and had no test: removed in round 6.)
+        if (!(cj > eps)) { *cond = cj; return PLM_OK; }
+        const double r2 = std::max(0.0, cj * cj - *cond * *cond);     // the rounding's share
+        if (r2 >= 0.75 * eps * eps || ++n_cert > 8) {     // the target would fall below eps / 2
+            // float32 fields cannot carry this stop rule (a rule far below 1e-3, or a very deep alignment): the
+            // fit ends by the rule on its own (f64-field) point and says what the rounding adds
+            rounding_note = std::sqrt(r2);
+            return PLM_OK;
         }
+        eps_eff = std::min(0.9 * eps_eff, std::sqrt(eps * eps - r2));
+        *done = false;
+        return PLM_OK;
     }
+    int anchor_buffers() {      // allocated by the first fit that skips a pair
+        if (c->xa) return PLM_OK;
+        PLM_TRY(plm_dalloc(&c->xa, (size_t)n));
+        PLM_TRY(plm_dalloc(&c->ga, (size_t)n));
+        return PLM_OK;
+    }
+};
+}  // namespace
+}  // extern "C++"
+
+// L-BFGS with a More'-Thuente line search (lbfgs_minimize of plm_lbfgs_driver.h over CtxProblem).  Defaults follow
+// libLBFGS (m = 6, ftol 1e-4, gtol 0.9, <= 20 trial steps), which plmc bundles [recollection, SURVEY.md App. C.4].
+int plm_ctx_optimize(plm_ctx_t *c, plm_iter_cb cb, void *user, plm_result_t *res) {
+    if (!c) return fail(PLM_EINVAL, "NULL ctx");
+    if (!c->have_weights) return fail(PLM_EINVAL, "weights not set");
+    PLM_HIP(hipSetDevice(c->device));
+    const double eps = c->prob.epsilon > 0 ? c->prob.epsilon : 1e-3;
+    const double t0 = lbfgs_now();
+    CtxProblem p{c, eps, std::min(20, c->prob.lbfgs_m > 0 ? c->prob.lbfgs_m : 6)};
+    LbfgsOutcome o;
+    PLM_TRY(lbfgs_minimize(p, LbfgsLimits{p.m, eps, c->prob.max_iter, cb, user, t0}, &o));
     PLM_HIP(hipStreamSynchronize(c->st));
-    c->eval_valid = true;   // every exit path above leaves the last accepted point in (x, g)
-    c->hj_at_x = vp && status != PLM_STATUS_LINESEARCH;   // a failed line search ends on a rejected trial's potentials
-    c->eval_vp = vp;
+    c->eval_valid = true;   // every exit path of the iteration leaves the last accepted point in (x, g)
+    c->hj_at_x = p.vp && o.status != PLM_STATUS_LINESEARCH;   // a failed line search ends on a rejected trial's potentials
+    c->eval_vp = p.vp;
     c->eval_accurate = c->fwd_accurate;
-    c->last_fx = fx;
-    c->last_nll = nll;
-    c->last_gh2 = gh2;
+    c->last_fx = o.fx;
+    c->last_nll = o.nll;
+    c->last_gh2 = p.gh2;
     if (res) {
-        res->iters_done = k;
+        res->iters_done = o.k;
         res->n_evals = c->n_evals;
-        res->status = status;
-        res->fx = fx;
+        res->status = o.status;
+        res->fx = o.fx;
         res->n_eff = (float)c->n_eff;
-        res->seconds_optimize = now_s() - t0;
+        res->seconds_optimize = lbfgs_now() - t0;
         // a fit that did not meet the stop rule says how far it got: the reference records this string as
         // `optimization_status` (couplings/tools.py:99), the only place a pipeline user sees it
-        if (status == PLM_STATUS_CONVERGED && rounding_note > 0)
+        if (o.status == PLM_STATUS_CONVERGED && p.rounding_note > 0)
             snprintf(res->status_msg, sizeof res->status_msg,
-                     "%s; float32 rounding of the fields adds %.1e", status_text(status), rounding_note);
-        else if (status == PLM_STATUS_LINESEARCH)
-            snprintf(res->status_msg, sizeof res->status_msg, "%s [code %d]; |g|/max(1,|x|) = %.3e", status_text(status),
-                     ls_reason, last_cond);
-        else if (status == PLM_STATUS_MAXITER || status == PLM_STATUS_INTERRUPTED)
+                     "%s; float32 rounding of the fields adds %.1e", status_text(o.status), p.rounding_note);
+        else if (o.status == PLM_STATUS_LINESEARCH)
+            snprintf(res->status_msg, sizeof res->status_msg, "%s [code %d]; |g|/max(1,|x|) = %.3e", status_text(o.status),
+                     o.ls_reason, o.cond);
+        else if (o.status == PLM_STATUS_MAXITER || o.status == PLM_STATUS_INTERRUPTED)
             snprintf(res->status_msg, sizeof res->status_msg, "%s; |g|/max(1,|x|) = %.3e (epsilon %.1e)",
-                     status_text(status), last_cond, eps);
+                     status_text(o.status), o.cond, eps);
         else
-            snprintf(res->status_msg, sizeof res->status_msg, "%s", status_text(status));
+            snprintf(res->status_msg, sizeof res->status_msg, "%s", status_text(o.status));
     }
     return PLM_OK;
 }

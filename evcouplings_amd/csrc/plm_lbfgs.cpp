@@ -1,5 +1,5 @@
-// plm_lbfgs.cpp -- More'-Thuente line search and L-BFGS pair history of plm_ctx_optimize (plm_lbfgs.h): scalar host
-// code, and the two host-only diagnostic entries that run it without a device.
+// plm_lbfgs.cpp -- More'-Thuente line search and L-BFGS pair history of lbfgs_minimize (plm_lbfgs.h; the iteration that
+// plm_ctx_optimize and plm_ar_fit run is plm_lbfgs_driver.h): scalar host code, and the two host-only diagnostic entries that run it without a device.
 #include "../../include/plm_hip.h"
 #include "plm_lbfgs.h"
 

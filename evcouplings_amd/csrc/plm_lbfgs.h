@@ -1,6 +1,7 @@
 // plm_lbfgs.h -- the scalar side of the optimiser: More'-Thuente line search and the L-BFGS pair history.
-// Host arithmetic in double only: no HIP header, no plm_ctx.  plm_ctx_optimize (plm_host.cpp) drives both with what
-// the device pass brings back; plm_linesearch_run / plm_lbfgs_admit (include/plm_hip.h) run them for the CPU tests.
+// Host arithmetic in double only: no HIP header, no plm_ctx.  lbfgs_minimize (plm_lbfgs_driver.h) drives both with what
+// the device pass brings back, for plm_ctx_optimize (plm_host.cpp) and plm_ar_fit (plm_ar.hip) alike; plm_linesearch_run /
+// plm_lbfgs_admit (include/plm_hip.h) run them for the CPU tests.
 #ifndef PLM_LBFGS_H
 #define PLM_LBFGS_H
 
@@ -13,7 +14,7 @@ int mt_update(double *stx, double *fx, double *dx, double *sty, double *fy, doub
 // the i-th newest LIVE slot of a ring of m history slots whose next pair goes to `end` (i = 0: slot end - 1)
 inline int lbfgs_live_slot(int m, int end, int i) { return (end + m - 1 - i) % m; }
 
-// One line search of plm_ctx_optimize: start(), then next() -> evaluate the trial -> feed() until feed() is non-zero.
+// One line search of lbfgs_minimize: start(), then next() -> evaluate the trial -> feed() until feed() is non-zero.
 struct MtSearch {
     // Defaults follow libLBFGS (ftol 1e-4, gtol 0.9, <= 20 trial steps)
     static constexpr int max_ls = 20;
