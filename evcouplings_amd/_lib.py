@@ -232,6 +232,26 @@ class PlmArFitResult(C.Structure):
                 ("fx", C.c_double), ("nll", C.c_double), ("gnorm", C.c_double), ("xnorm", C.c_double)]
 
 
+class PlmRbmSampleOpts(C.Structure):
+    _fields_ = [("n_chains", C.c_int32), ("burn_in", C.c_int32), ("n_snapshots", C.c_int32), ("thin", C.c_int32),
+                ("first_step", C.c_uint32), ("first_chain", C.c_uint32), ("seed", C.c_uint64),
+                ("start", C.c_void_p), ("fixed", C.c_void_p), ("allowed", C.c_void_p)]
+
+
+class PlmRbmFitOpts(C.Structure):
+    _fields_ = [("n_chains", C.c_int32), ("n_epochs", C.c_int32), ("steps_per_epoch", C.c_int32), ("first_epoch", C.c_int32),
+                ("lr_decay_after", C.c_int32), ("lr", C.c_double), ("lambda_g", C.c_double), ("lambda_w", C.c_double),
+                ("seed", C.c_uint64), ("start", C.c_void_p)]
+
+
+class PlmRbmFitResult(C.Structure):
+    _fields_ = [("x_out", C.c_void_p), ("data_out", C.c_void_p), ("model_out", C.c_void_p), ("chains_out", C.c_void_p),
+                ("trace", C.c_void_p), ("phase_ms", C.c_void_p), ("epochs_done", C.c_int32), ("status", C.c_int32)]
+
+
+RBM_EPOCH_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
+
+
 # every symbol include/plm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -345,6 +365,10 @@ SYMBOLS = [
                               C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     ("plm_ar_fit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlmArFitOpts), _P, ITER_CB, _P, C.c_int,
                              _P, _P, C.POINTER(PlmArFitResult)]),
+    ("plm_rbm_score", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int, _P, _P, _P]),
+    ("plm_rbm_sample", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmRbmSampleOpts), C.c_int, _P, _P, _P]),
+    ("plm_rbm_fit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmRbmFitOpts), C.c_int, _P,
+                              RBM_EPOCH_CB, _P, C.POINTER(PlmRbmFitResult)]),
 ]
 
 _lib = None

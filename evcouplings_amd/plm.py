@@ -576,6 +576,120 @@ def ar_fit(msa, weights, q, lambda_h, lambda_j, max_iter=1000, epsilon=1e-4, lbf
             "xnorm": res.xnorm}
 
 
+def rbm_n_params(L, q, M):
+    return L * q + M + M * L * q
+
+
+def _rbm_model(g, c, W, q):
+    """(params, L, M): the RBM layout g [L][q], c [M], W [M][L][q] as one float32 vector"""
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    if g.ndim != 2 or g.shape[1] != q:
+        raise ValueError("g must be an (L, %d) matrix" % q)
+    L = g.shape[0]
+    c = np.ascontiguousarray(c, dtype=np.float32).ravel()
+    M = c.size
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    if W.shape != (M, L, q):
+        raise ValueError("W must be an (M, L, q) = (%d, %d, %d) array" % (M, L, q))
+    return np.concatenate([g.ravel(), c, W.ravel()]), L, M
+
+
+def _rbm_split(x, L, q, M):
+    return x[:L * q].reshape(L, q), x[L * q:L * q + M], x[L * q + M:].reshape(M, L, q)
+
+
+def rbm_score(seqs, q, g, c, W, inputs=False, device=0):
+    """
+    score(v) = sum_i g_i(v_i) + sum_mu softplus(I_mu(v)) = log P(v) + log Z of a restricted Boltzmann machine with Potts
+    visible and Bernoulli hidden units (plm_rbm_score, DESIGN_NEXT_ROWS.md section 9.22), I_mu(v) = c_mu + sum_i W_mu,i(v_i).
+    g: L x q; c: M; W: M x L x q.  Returns the scores [n] (float64), with inputs also the hidden-unit inputs I [n, M].
+    """
+    q = int(q)
+    x, L, M = _rbm_model(g, c, W, q)
+    seqs = _msa(seqs)
+    if seqs.shape[1] != L:
+        raise ValueError("the sequences have %d sites, the model %d" % (seqs.shape[1], L))
+    n = seqs.shape[0]
+    score = np.zeros(n)
+    I = np.zeros((n, M)) if inputs else None
+    check(_lib.load().plm_rbm_score(_ptr(seqs), n, L, q, M, _ptr(x), int(device), None, _ptr(score), _ptr(I)))
+    return (score, I) if inputs else score
+
+
+def rbm_sample(g, c, W, q, n_chains, burn_in=10, n_snapshots=1, thin=1, seed=0, start=None, fixed=None, allowed=None,
+               first_step=0, first_chain=0, hidden=False, device=0):
+    """
+    Block Gibbs sampling of a restricted Boltzmann machine (plm_rbm_sample): n_chains independent chains, burn_in steps
+    (all hidden units given the sites, then all sites given the hidden units), then n_snapshots snapshots thin steps
+    apart.  start: None (one draw per site of softmax g_i) or n_chains x L states; fixed: None or L flags; allowed: None or
+    q flags.  Chain c of a call is chain first_chain + c of the seed whatever n_chains, and a run continues from its last
+    states with first_step = the steps made so far.
+    Returns the states int8 [K, C, L], with hidden also the hidden units int8 [K, C, M] of the step before each snapshot.
+    """
+    q, C_, K = int(q), int(n_chains), int(n_snapshots)
+    x, L, M = _rbm_model(g, c, W, q)
+    start, fixed, allowed = _chain_args(start, fixed, allowed, C_, L, q)
+    opts = _lib.PlmRbmSampleOpts(C_, int(burn_in), K, int(thin), int(first_step) & 0xFFFFFFFF, int(first_chain) & 0xFFFFFFFF,
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(start), _ptr(fixed), _ptr(allowed))
+    states = np.zeros((max(K, 0), max(C_, 0), L), dtype=np.int8)
+    hid = np.zeros((max(K, 0), max(C_, 0), M), dtype=np.int8) if hidden else None
+    check(_lib.load().plm_rbm_sample(L, q, M, _ptr(x), C.byref(opts), int(device), None, _ptr(states), _ptr(hid)))
+    return (states, hid) if hidden else states
+
+
+RBM_STATUS = {_lib.STATUS_MAXITER: "maxiter", _lib.STATUS_INTERRUPTED: "interrupted"}
+
+
+def rbm_fit(msa, weights, q, g, c, W, n_chains, n_epochs, steps_per_epoch=2, lr=0.1, lr_decay_after=0, lambda_g=0.0,
+            lambda_w=0.0, seed=0, start=None, first_epoch=0, callback=None, phase_times=False, device=0):
+    """
+    Persistent contrastive divergence for a restricted Boltzmann machine (plm_rbm_fit): n_epochs steps of
+    theta <- theta + lr_g ((D - N) - 2 lambda theta) from the start point (g, c, W), where D are the statistics of the
+    weighted alignment and N those of n_chains persistent block-Gibbs chains after steps_per_epoch steps, both with the
+    hidden units summed out.  lr_decay_after = T > 0: the step of global epoch e is lr T / (e + 1) once e + 1 > T.  start:
+    None (the sampler's start rule) or n_chains x L states; first_epoch: the global number of the first epoch, for a call
+    that continues an earlier one from its g, c, W and chains.  callback(epoch, max_dg, max_dc, max_dw, lr, data_score)
+    is called once per epoch and stops the fit by returning a true value.
+    Returns a dict: g, c, W (float32), data and model (the statistics of the last epoch that ran, each a (g, c, W) triple
+    of float64), chains (int8 C x L), trace (one row per epoch that ran: max |D_g - N_g|, max |D_c - N_c|,
+    max |D_W - N_W|, lr_g, the weighted mean score of the alignment), epochs_done (updates applied), status ("maxiter",
+    "interrupted").  The result is bitwise reproducible.  phase_times: also phase_ms, the milliseconds of (data
+    statistics, chain steps, model statistics and trace row, update) summed over the epochs, by device events; the
+    fit then waits for the device after every epoch.
+    """
+    q, C_, E = int(q), int(n_chains), int(n_epochs)
+    x0, L, M = _rbm_model(g, c, W, q)
+    msa = _msa(msa)
+    if msa.shape[1] != L:
+        raise ValueError("the alignment has %d sites, the model %d" % (msa.shape[1], L))
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.shape != (msa.shape[0],):
+        raise ValueError("need one weight per sequence")
+    start = _chain_args(start, None, None, C_, L, q)[0]
+    opts = _lib.PlmRbmFitOpts(C_, E, int(steps_per_epoch), int(first_epoch), int(lr_decay_after), float(lr), float(lambda_g),
+                              float(lambda_w), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(start))
+    n = x0.size
+    x = np.zeros(n, np.float32)
+    data, model = np.zeros(n), np.zeros(n)
+    chains = np.zeros((max(C_, 0), L), np.int8)
+    trace = np.zeros((max(E, 0), 5))
+    phase = np.zeros(4) if phase_times else None
+    res = _lib.PlmRbmFitResult(_ptr(x), _ptr(data), _ptr(model), _ptr(chains), _ptr(trace), _ptr(phase), 0, 0)
+    cb, reraise = _stop_callback(_lib.RBM_EPOCH_CB, callback, lambda epoch, *row: (int(epoch),) + row)
+    rc = _lib.load().plm_rbm_fit(_ptr(msa), _ptr(w), msa.shape[0], L, q, M, _ptr(x0), C.byref(opts), int(device), None, cb,
+                                 None, C.byref(res))
+    reraise()
+    check(rc)
+    done = int(res.epochs_done)
+    rows = done if res.status == _lib.STATUS_MAXITER else done + 1
+    go, co, Wo = (a.copy() for a in _rbm_split(x, L, q, M))
+    out = dict(g=go, c=co, W=Wo, data=_rbm_split(data, L, q, M), model=_rbm_split(model, L, q, M), chains=chains,
+               trace=trace[:rows].copy(), epochs_done=done, status=RBM_STATUS[int(res.status)])
+    if phase_times:
+        out["phase_ms"] = phase
+    return out
+
+
 def sample_plan(L, q, n_chains, n_cu=0):
     """
     The launch plan `sample` and `bm_fit` use for L sites, q states and n_chains chains (plm_sample_plan,

@@ -1098,6 +1098,112 @@ int plm_ar_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t 
                const plm_ar_fit_opts *opts, const float *x_start, plm_iter_cb cb, void *user, int device, void *stream,
                float *x_out, plm_ar_fit_result *result);
 
+/* ---- A restricted Boltzmann machine on an alignment (DESIGN_NEXT_ROWS.md section 9.22) --------------------------------
+ * Potts visible units v_i in 0..q-1 at the sites i = 0 .. L-1 and M Bernoulli hidden units h_mu in {0, 1} (Tubiana, Cocco,
+ * Monasson 2019):
+ *     I_mu(v)   = c_mu + sum_i W_mu,i(v_i)
+ *     P(v, h)   ~ exp( sum_i g_i(v_i) + sum_mu h_mu I_mu(v) )
+ *     score(v)  = sum_i g_i(v_i) + sum_mu softplus(I_mu(v))            = log P(v) + log Z
+ *     P(h_mu = 1 | v) = sigma(I_mu(v)),    P(v_i = a | h) = softmax_a( g_i(a) + sum_mu h_mu W_mu,i(a) )
+ * Parameters ("the RBM layout"): one float32 vector, g [L][q], then c [M], then W [M][L][q]: L q + M + M L q values.
+ * q in 2..32 (PLM_EUNSUPPORTED otherwise), L >= 1, M >= 1, M L q below 2^31 (and M at most 64 x 65535, else
+ * PLM_EUNSUPPORTED).  In all three calls the arguments are checked before the device is looked at (PLM_EINVAL: NULL
+ * arguments, sizes below 1, rows x L at or above 2^31, states outside 0..q-1 and what each call names below), and
+ * PLM_ENOMEM is decided before any allocation.  log Z is not computed here.
+ *
+ * plm_rbm_score: score_out [n] and inputs_out [n][M] (or NULL), float64.  I_mu is accumulated in float64 from (double) c_mu,
+ *   then one add per site i = 0 .. L-1 in that order of (double) W_mu,i(v_i); softplus(I) = max(I, 0) + log1p(exp(-|I|));
+ *   the score is one running sum: the fields in site order, then the softplus terms in mu order.  The result depends on
+ *   (sequence, model) only, not on n or the place of the row in the call.
+ *
+ * plm_rbm_sample: block Gibbs sampling with C independent chains; states_out [K][C][L], hidden_out [K][C][M] (or NULL).
+ *   Step t of chain c (the steps count from first_step across burn-in, thinning and snapshots, as plm_sample counts its
+ *   sweeps: snapshot 0 after burn_in steps, every further one thin steps later):
+ *   (a) hidden draw: for every mu, I_mu in float32 is c_mu, then one float32 add per site i = 0 .. L-1 in that order of
+ *       W_mu,i(v_i); p = 1 / (1 + expf(-I)); h_mu = 1 iff u < p, u = ((word0 >> 8) + 0.5) 2^-24 (kept below 1) of
+ *       Philox4x32-10 with the counter (first_chain + c, 2, t, mu);
+ *   (b) visible draw: for every site that is not fixed, U_a = g_i(a), then one float32 add of W_mu,i(a) for every mu with
+ *       h_mu = 1, in mu order; the new state is the draw of plm_sample's contract over the allowed states at beta = 1
+ *       with the counter (first_chain + c, 0, t, i).
+ *   The key is (seed low, seed high).  start == NULL: chain c begins from one such draw per site of softmax g_i with the
+ *   counter (first_chain + c, 0, 0xFFFFFFFF, i).  hidden_out holds the h drawn in the step that produced each snapshot
+ *   (zeros for a snapshot no step produced: burn_in = 0).  Chain c is the same chain whatever n_chains, the launch plan
+ *   (PLM_RBM_WAVES=1|2|4|8 forces the waves that share a tile of 64 chains: measurements and tests only), or how a run is cut into
+ *   calls by first_chain, or by first_step with the last states as start.  PLM_EINVAL also: no allowed state, start
+ *   states that are not allowed at a site that is not fixed, first_chain + n_chains above 2^32, a step index at or above
+ *   2^32 - 1.  PLM_EUNSUPPORTED: the states and hidden units of 64 chains do not fit the LDS of a CU (L / 4 + M / 32
+ *   words per chain: L + M / 8 up to about 2 500).
+ *
+ * plm_rbm_fit: persistent contrastive divergence by plain gradient ascent from x_start (required).  Chains begin at
+ *   opts->start, or from the start rule at the parameters of the call's first epoch.  Local epoch e = 0 .. n_epochs - 1,
+ *   global epoch g = first_epoch + e:
+ *   1. data statistics at the current parameters, float64: p_s,mu = sigma(I_mu(x_s)) with I as in plm_rbm_score;
+ *      D_g[i][a] = sum_s w_s delta(x_si, a) / N_eff (computed once), D_c[mu] = sum_s w_s p_s,mu / N_eff,
+ *      D_W[mu][i][a] = sum_s (w_s p_s,mu) delta(x_si, a) / N_eff; N_eff = sum_s w_s in sequence order; the division
+ *      follows the sum
+ *   2. every chain makes steps_per_epoch = k steps of plm_rbm_sample's contract (first_chain = 0, all states allowed, no
+ *      fixed sites) with the step indices g k .. g k + k - 1
+ *   3. model statistics from the chains' visible states after those steps, Rao-Blackwellised over the hidden units:
+ *      p_c,mu = sigma(I_mu(v_c)) in float64; N_g exact counts over C; N_c, N_W as in step 1 with weight 1 and divisor C
+ *   4. trace row e = (max |D_g - N_g|, max |D_c - N_c|, max |D_W - N_W|, lr_g, sum_s w_s score(x_s) / N_eff) with
+ *      lr_g = lr when lr_decay_after == 0 or g + 1 <= lr_decay_after, else lr lr_decay_after / (g + 1), in float64
+ *   5. the callback is called with the global epoch and the row; a non-zero return stops before the update
+ *      (PLM_STATUS_INTERRUPTED, epochs_done = e)
+ *   6. theta <- (float)( (double) theta + lr_g ((D - N) - (2 lambda) theta) ), lambda = lambda_g on g, 0 on c, lambda_w on
+ *      W: every operation in float64, the sum rounded to float32 once
+ *   After n_epochs updates the status is PLM_STATUS_MAXITER.  Every sum over sequences or chains is made in an order the
+ *   shape alone fixes, without floating-point atomics: two calls return the same bytes, and E epochs equal E1 + E2 epochs
+ *   resumed from x_out, chains_out and first_epoch = E1.  Every output pointer may be NULL; data_out and model_out are
+ *   the statistics D and N of the last epoch that ran, in the RBM layout.  PLM_EINVAL also: a weight that is negative or
+ *   not finite, weights that sum to zero, lr, lambda_g or lambda_w negative or not finite, (first_epoch + n_epochs)
+ *   steps_per_epoch at or above 2^32 - 1. */
+typedef struct {
+    int32_t  n_chains;      /* C >= 1, independent chains                                            */
+    int32_t  burn_in;       /* steps before the first snapshot, >= 0                                 */
+    int32_t  n_snapshots;   /* K >= 1 snapshots of all chains                                        */
+    int32_t  thin;          /* steps between snapshots, >= 1 (unused when K == 1)                    */
+    uint32_t first_step;    /* the index of the call's first step                                    */
+    uint32_t first_chain;   /* the chain index of the call's first chain                             */
+    uint64_t seed;
+    const int8_t  *start;   /* NULL, or C x L states                                                 */
+    const uint8_t *fixed;   /* NULL, or L flags: sites that are never resampled                      */
+    const uint8_t *allowed; /* NULL, or q flags: states that may be drawn (at least one set)         */
+} plm_rbm_sample_opts;
+typedef struct {
+    int32_t  n_chains;          /* C >= 1 persistent chains                                          */
+    int32_t  n_epochs;          /* E >= 1 epochs of this call                                        */
+    int32_t  steps_per_epoch;   /* k >= 1                                                            */
+    int32_t  first_epoch;       /* e0 >= 0: global number of this call's first epoch (continuation)  */
+    int32_t  lr_decay_after;    /* T >= 0: the step decays as T / (g + 1) after global epoch T - 1   */
+    double   lr;                /* step, >= 0                                                        */
+    double   lambda_g;          /* >= 0, on the fields                                               */
+    double   lambda_w;          /* >= 0, on the weights                                              */
+    uint64_t seed;
+    const int8_t *start;        /* NULL, or C x L states                                             */
+} plm_rbm_fit_opts;
+typedef struct {
+    float  *x_out;       /* parameters after the last applied update, RBM layout                     */
+    double *data_out;    /* D of the last epoch that ran, RBM layout                                 */
+    double *model_out;   /* N of the last epoch that ran, RBM layout                                 */
+    int8_t *chains_out;  /* C x L states of the last epoch that ran                                  */
+    double *trace;       /* n_epochs x 5, one row per epoch that ran                                 */
+    double *phase_ms;    /* NULL, or 4 doubles: milliseconds of (data statistics, chain steps, model  */
+                         /* statistics and trace row, update) summed over the epochs whose update    */
+                         /* was applied, by device events; a timed fit waits for every epoch         */
+    int32_t epochs_done; /* updates applied                                                          */
+    int32_t status;      /* PLM_STATUS_MAXITER or PLM_STATUS_INTERRUPTED                             */
+} plm_rbm_fit_result;
+/* Called once per epoch after its trace row is known and before its update, with the global epoch number. */
+typedef int (*plm_rbm_epoch_cb)(int32_t epoch, double max_dg, double max_dc, double max_dw, double lr, double data_score,
+                                void *user);
+int plm_rbm_score(const int8_t *seqs, int32_t n_seqs, int32_t n_sites, int32_t n_states, int32_t n_hidden,
+                  const float *params, int device, void *stream, double *score_out, double *inputs_out);
+int plm_rbm_sample(int32_t n_sites, int32_t n_states, int32_t n_hidden, const float *params, const plm_rbm_sample_opts *opts,
+                   int device, void *stream, int8_t *states_out, int8_t *hidden_out);
+int plm_rbm_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states, int32_t n_hidden,
+                const float *x_start, const plm_rbm_fit_opts *opts, int device, void *stream, plm_rbm_epoch_cb cb, void *user,
+                plm_rbm_fit_result *result);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
