@@ -249,6 +249,14 @@ class PlmRbmFitResult(C.Structure):
                 ("trace", C.c_void_p), ("phase_ms", C.c_void_p), ("epochs_done", C.c_int32), ("status", C.c_int32)]
 
 
+class PlmCrossOpts(C.Structure):
+    _fields_ = [("skip_state", C.c_int32), ("want_best", C.c_int32)]
+
+
+class PlmCrossBest(C.Structure):
+    _fields_ = [("index", C.c_int64), ("best", C.c_double), ("second", C.c_double)]
+
+
 RBM_EPOCH_CB = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
 
 
@@ -369,6 +377,9 @@ SYMBOLS = [
     ("plm_rbm_sample", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmRbmSampleOpts), C.c_int, _P, _P, _P]),
     ("plm_rbm_fit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmRbmFitOpts), C.c_int, _P,
                               RBM_EPOCH_CB, _P, C.POINTER(PlmRbmFitResult)]),
+    ("plm_cross_energies", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P,
+                                     C.POINTER(PlmCrossOpts), C.c_int, _P, _P, _P, _P]),
+    ("plm_group_assignment", C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P]),
 ]
 
 _lib = None

@@ -1312,6 +1312,120 @@ def top_combinations(target, q, hi, jij, sites, letters=None, top=100, device=0,
     return idx, en
 
 
+# ---- inter-protein energies of two sequence sets, and matching by them (DESIGN_NEXT_ROWS.md section 9.23) ----
+CROSS_BEST = np.dtype([("index", np.int64), ("best", np.float64), ("second", np.float64)])
+
+
+def inter_blocks(jij, L, q, sites_a, sites_b, gauge="zero_sum"):
+    """
+    The inter block of a model for `plm.cross_energies`: a (len(sites_a), len(sites_b), q, q) float32 array with
+    out[k, l, a, b] = J_ij(a, b) for i = sites_a[k], j = sites_b[l], from the canonical i<j blocks jij
+    [L(L-1)/2][q][q] (a block is transposed where sites_a[k] > sites_b[l]).  The site lists are arbitrary but disjoint.
+    The energy of the inter block alone depends on the gauge: a gauge change moves energy between the inter block, the
+    intra blocks and the fields, and only their sum is invariant.  gauge="zero_sum" (the default) therefore brings every
+    block to the zero-sum gauge, J'(a,b) = J(a,b) - mean_b J(a,.) - mean_a J(.,b) + mean J, in float64 before the one
+    rounding to float32, which leaves the part of the energy that no single-site term can absorb; gauge=None takes the
+    values as they are.  Pure numpy.
+    """
+    if gauge not in ("zero_sum", None):
+        raise ValueError("gauge must be 'zero_sum' or None (got %r)" % (gauge,))
+    L, q = int(L), int(q)
+    jij = np.asarray(jij)
+    if jij.size != L * (L - 1) // 2 * q * q:
+        raise ValueError("jij must hold %d blocks of %d x %d values" % (L * (L - 1) // 2, q, q))
+    jij = jij.reshape(L * (L - 1) // 2, q, q)
+    sa, sb = np.asarray(sites_a, dtype=np.int64).ravel(), np.asarray(sites_b, dtype=np.int64).ravel()
+    if sa.size < 1 or sb.size < 1:
+        raise ValueError("each side needs one site at least")
+    both = np.concatenate([sa, sb])
+    if both.min() < 0 or both.max() >= L:
+        raise ValueError("sites must lie in 0..%d" % (L - 1))
+    if np.unique(both).size != both.size:
+        raise ValueError("the two site lists must be disjoint and name no site twice")
+    i, j = sa[:, None], sb[None, :]
+    lo, hi = np.minimum(i, j), np.maximum(i, j)
+    blocks = jij[lo * (2 * L - lo - 1) // 2 + (hi - lo - 1)]                   # (LA, LB, q, q), [state at lo][state at hi]
+    out = np.where((i < j)[:, :, None, None], blocks, blocks.transpose(0, 1, 3, 2))
+    if gauge == "zero_sum":
+        out = out.astype(np.float64)
+        out = (out - out.mean(axis=3, keepdims=True) - out.mean(axis=2, keepdims=True)
+               + out.mean(axis=(2, 3), keepdims=True))
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def _group_offsets(a_offsets, b_offsets, n_a, n_b):
+    if (a_offsets is None) != (b_offsets is None):
+        raise ValueError("a_offsets and b_offsets go together")
+    if a_offsets is None:
+        return np.array([0, n_a], np.int64), np.array([0, n_b], np.int64)
+    ao = np.ascontiguousarray(a_offsets, dtype=np.int64).ravel()
+    bo = np.ascontiguousarray(b_offsets, dtype=np.int64).ravel()
+    if ao.size != bo.size or ao.size < 1:
+        raise ValueError("a_offsets and b_offsets must hold n_groups + 1 entries each")
+    return ao, bo
+
+
+def cross_block_offsets(a_offsets, b_offsets):
+    """Where each group's n_a(g) x n_b(g) block starts in the flat matrix of `cross_energies`: int64 [n_groups + 1]."""
+    ao, bo = np.asarray(a_offsets, np.int64), np.asarray(b_offsets, np.int64)
+    return np.concatenate([[0], np.cumsum(np.diff(ao) * np.diff(bo))]).astype(np.int64)
+
+
+def cross_energies(jab, seqs_a, seqs_b, a_offsets=None, b_offsets=None, skip_state=None, matrix=True, best=True, device=0):
+    """
+    Inter-protein coupling energies E(s,t) = sum_i sum_j jab[i, j, a_si, b_tj] between rows of seqs_a (n_a x L_A states)
+    and rows of seqs_b (n_b x L_B states); jab is the (L_A, L_B, q, q) float32 array of `inter_blocks`.  Group g pairs the
+    rows a_offsets[g]:a_offsets[g+1] of A with the rows b_offsets[g]:b_offsets[g+1] of B (no offsets: one group, the
+    all-against-all table).  A term whose state on either side equals skip_state is left out.  All sums are float64 in a
+    fixed order: the same input gives the same bits.  Returns a dict:
+      matrix         flat float64, the groups' row-major n_a(g) x n_b(g) blocks one after the other (None with matrix=False)
+      block_offsets  int64 [n_groups + 1], where each block starts
+      rows_best      structured array [n_a] (index, best, second): the row of B of the same group with the largest E (ties
+                     to the smallest index; -1 without partners), that E, and the largest E over the other partners (-inf
+                     where there is none);  cols_best [n_b] likewise for the rows of B.  None with best=False, which with
+                     matrix=False leaves nothing to compute and is refused.
+    """
+    lib = _lib.load()
+    jab = np.ascontiguousarray(jab, dtype=np.float32)
+    if jab.ndim != 4 or jab.shape[2] != jab.shape[3]:
+        raise ValueError("jab must be an (L_A, L_B, q, q) array")
+    LA, LB, q, _ = jab.shape
+    seqs_a, seqs_b = _msa(seqs_a), _msa(seqs_b)
+    if seqs_a.shape[1] != LA or seqs_b.shape[1] != LB:
+        raise ValueError("seqs_a must have %d columns and seqs_b %d (got %d and %d)" % (LA, LB, seqs_a.shape[1],
+                                                                                         seqs_b.shape[1]))
+    n_a, n_b = seqs_a.shape[0], seqs_b.shape[0]
+    ao, bo = _group_offsets(a_offsets, b_offsets, n_a, n_b)
+    if not matrix and not best:
+        raise ValueError("nothing to compute: matrix=False and best=False")
+    block_offsets = cross_block_offsets(ao, bo)
+    opts = _lib.PlmCrossOpts(-1 if skip_state is None else int(skip_state), 1 if best else 0)
+    m = np.empty(max(int(block_offsets[-1]), 0)) if matrix else None
+    rows = np.empty(n_a, CROSS_BEST) if best else None
+    cols = np.empty(n_b, CROSS_BEST) if best else None
+    check(lib.plm_cross_energies(_ptr(jab), LA, LB, q, _ptr(seqs_a), n_a, _ptr(seqs_b), n_b, ao.size - 1, _ptr(ao), _ptr(bo),
+                                 C.byref(opts), int(device), None, _ptr(m), _ptr(rows), _ptr(cols)))
+    return dict(matrix=m, block_offsets=block_offsets, rows_best=rows, cols_best=cols)
+
+
+def group_assignment(scores, a_offsets, b_offsets, maximize=True):
+    """
+    The exact rectangular linear assignment of every group of a score table laid out as the matrix of `cross_energies`:
+    min(n_a(g), n_b(g)) pairs per group with the largest (or, maximize=False, smallest) total score.  Host code of the
+    library, no device.  Returns (partner_of_a int64 [n_a]: the global row of B or -1, totals float64 [n_groups]).
+    """
+    lib = _lib.load()
+    scores = np.ascontiguousarray(scores, dtype=np.float64).ravel()
+    ao, bo = _group_offsets(a_offsets, b_offsets, 0, 0)
+    if int((np.diff(ao) * np.diff(bo)).sum()) != scores.size:
+        raise ValueError("scores must hold one value per pair of every group")
+    partner = np.empty(max(int(ao[-1]), 0), np.int64)
+    totals = np.empty(ao.size - 1)
+    check(lib.plm_group_assignment(_ptr(scores), ao.size - 1, _ptr(ao), _ptr(bo), 1 if maximize else 0, _ptr(partner),
+                                   _ptr(totals)))
+    return partner, totals
+
+
 # ---- the L-BFGS vector kernels, test-facing (diagnostic: tests/test_gpu_lbfgs_vectors.py) ----
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)

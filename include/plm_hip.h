@@ -1204,6 +1204,53 @@ int plm_rbm_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t
                 const float *x_start, const plm_rbm_fit_opts *opts, int device, void *stream, plm_rbm_epoch_cb cb, void *user,
                 plm_rbm_fit_result *result);
 
+/* ---- inter-protein coupling energies of two sequence sets, and matching by them (DESIGN_NEXT_ROWS.md section 9.23) ----
+ * For a row s of A (n_sites_a states) and a row t of B (n_sites_b states) of the same group
+ *     E(s,t) = sum_{i in A} sum_{j in B} J_ij(a_si, b_tj)
+ * jab: the inter block of a model alone, [n_sites_a][n_sites_b][q][q] float32, jab[i][j][a][b] = J_ij(a,b), assumed
+ * finite (the energy of the inter block alone depends on the gauge: plm.inter_blocks of the Python side extracts it in
+ * the zero-sum gauge).  seqs_a [n_a][n_sites_a], seqs_b [n_b][n_sites_b]: states 0..q-1, row-major.
+ * Groups: a_offsets and b_offsets [n_groups + 1], non-decreasing from 0 to n_a / n_b; group g pairs the rows
+ * a_offsets[g] .. a_offsets[g+1]-1 of A with the rows b_offsets[g] .. b_offsets[g+1]-1 of B; either side may be empty; one
+ * group is the all-against-all table.  n_groups = 0 (with n_a = n_b = 0) is PLM_OK and writes nothing.
+ * Arithmetic (fixed, so that a twin can follow it to the bit):
+ *     V[t][i][a] = sum_j (double) jab[i][j][a][b_tj]     j ascending, float64, from +0.0
+ *     E[s][t]    = sum_i V[t][i][a_si]                   i ascending, float64, from +0.0
+ * A term whose state equals skip_state is left out (a b_tj in the first sum, an a_si in the second).  Only additions
+ * of float32 values widened to double, no floating-point atomics: the result does not depend on tile sizes, on how groups
+ * share workgroups, on the chunks of V, or on the device.  PLM_CROSS_TILE (rows of A per workgroup) and PLM_CROSS_VCHUNK
+ * (64-row tiles of B per V buffer), positive integers, force the plan: measurements and tests only.
+ * Outputs, each optional (but one at least):
+ *   matrix_out  the groups' row-major n_a(g) x n_b(g) blocks, concatenated in group order
+ *   rows_best   [n_a]: index = the row of B in the row's group with the largest E (a global row index, ties to the smallest
+ *               index), best = that E, second = the largest E over the other partners (-inf with one partner; index -1 and
+ *               both -inf with none);  cols_best [n_b]: the same for every row of B over the rows of A.
+ *               Both are filled only when opts->want_best is not 0.
+ * PLM_EINVAL (with a message, before the device is looked at): NULL jab, seqs, offsets or opts; nothing to write; a side
+ * with fewer than 1 site; negative counts; offsets that do not start at 0, decrease or end elsewhere than n_a / n_b; a
+ * state outside 0..q-1; skip_state outside -1..q-1; a PLM_CROSS_TILE or PLM_CROSS_VCHUNK that is no positive integer.
+ * PLM_EUNSUPPORTED: q outside 2..32.  PLM_ENOMEM before any allocation, from jab, the sequences, V and the outputs.
+ *
+ * plm_group_assignment (host code, no device): per group the exact rectangular linear assignment on `scores` (laid out
+ * as matrix_out): min(n_a(g), n_b(g)) pairs with the largest (maximize != 0) or smallest total score, by shortest
+ * augmenting paths, O(n^2 m).  partner_of_a [n_a]: the global row of B, or -1; totals [n_groups] or NULL: the sum of the
+ * chosen scores, over the rows of A in order.  PLM_EINVAL: NULL arguments, malformed offsets, a score that is not finite. */
+typedef struct {
+    int32_t skip_state;     /* -1: none; else a term whose a- or b-state equals it is omitted */
+    int32_t want_best;      /* fill the best-partner arrays */
+} plm_cross_opts;
+typedef struct {
+    int64_t index;
+    double best;
+    double second;
+} plm_cross_best;
+int plm_cross_energies(const float *jab, int32_t n_sites_a, int32_t n_sites_b, int32_t n_states, const int8_t *seqs_a,
+                       int64_t n_a, const int8_t *seqs_b, int64_t n_b, int64_t n_groups, const int64_t *a_offsets,
+                       const int64_t *b_offsets, const plm_cross_opts *opts, int device, void *stream, double *matrix_out,
+                       plm_cross_best *rows_best, plm_cross_best *cols_best);
+int plm_group_assignment(const double *scores, int64_t n_groups, const int64_t *a_offsets, const int64_t *b_offsets,
+                         int32_t maximize, int64_t *partner_of_a, double *totals);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
