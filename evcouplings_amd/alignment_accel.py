@@ -33,19 +33,23 @@ def _gpu_weights(seq_weights):
     return w.astype(np.float32)
 
 
-def _int8_states(a, what):
+def _int8_states(a, what, top=127):
     """Integer states as the int8 the library takes; values outside 0..127 would wrap silently in the cast (and the
-    packed byte compares assume bytes < 0x80), so they are refused here."""
+    packed byte compares assume bytes < 0x80), so they are refused here.  `top`: a lower limit of the caller's."""
     a = np.asarray(a)
-    if a.size and (a.min() < 0 or a.max() > 127):
-        raise ValueError("%s holds states outside 0..127 (min %d, max %d)" % (what, a.min(), a.max()))
+    if a.size and (a.min() < 0 or a.max() > top):
+        raise ValueError("%s holds states outside 0..%d (min %d, max %d)" % (what, top, a.min(), a.max()))
     return np.ascontiguousarray(a, dtype=np.int8)
 
 
+REWEIGHT_MAX_STATE = 123       # PLM_REWEIGHT_MAX_STATE (include/plm_hip.h): 124..127 are fill bytes of the kernels
+
+
 def num_cluster_members(matrix, identity_threshold):
-    """Drop-in for alignment.num_cluster_members: length-N float64 vector of cluster sizes (self included)."""
+    """Drop-in for alignment.num_cluster_members: length-N float64 vector of cluster sizes (self included).
+    States are 0..123 (a ValueError otherwise, before the library is called)."""
     from evcouplings_amd import plm
-    return plm.reweight(_int8_states(matrix, "matrix"), float(identity_threshold)).astype(np.float64)
+    return plm.reweight(_int8_states(matrix, "matrix", REWEIGHT_MAX_STATE), float(identity_threshold)).astype(np.float64)
 
 
 def frequencies(matrix, seq_weights, num_symbols):

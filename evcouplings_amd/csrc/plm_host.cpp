@@ -2041,16 +2041,22 @@ int plm_reweight(const int8_t *msa, int32_t n_seqs, int32_t n_sites, double thet
 int plm_reweight_ex(const int8_t *msa, int32_t n_seqs, int32_t n_sites, double theta_id, int32_t flags,
                     int32_t *counts_out) {
     if (!msa || !counts_out) return fail(PLM_EINVAL, "NULL argument");
-    // reweighting compares raw bytes; any state value 0..126 is legal here, so borrow q = 21
-    // only for the context's tiling and validate the range ourselves
+    if (n_seqs <= 0 || n_sites <= 0) return fail(PLM_EINVAL, "need n_seqs > 0 and n_sites > 0");
+    // reweighting compares raw bytes; any state value 0..123 is legal here, so borrow q = 21
+    // only for the context's tiling and validate the range ourselves.  124..126 are the kernels' own fill values
+    // (0x7c for my gaps under -g, 0x7d / 0x7e past the end of a row): an alignment byte of that value would match them
     for (size_t k = 0; k < (size_t)n_seqs * n_sites; k++)
-        if (msa[k] < 0 || msa[k] > 126) return fail(PLM_EINVAL, "msa[%zu] outside 0..126", k);
-    plm_problem_t p = basic_problem(msa, n_seqs, n_sites, 21);
+        if (msa[k] < 0 || msa[k] > PLM_REWEIGHT_MAX_STATE)
+            return fail(PLM_EINVAL, "msa[%zu] = %d outside 0..%d", k, (int)msa[k], PLM_REWEIGHT_MAX_STATE);
+    // a model needs two sites (make_dims), cluster sizes are defined for one column as well: the tiling of a two-site
+    // problem, which is the same up to L = 32, with the real L for the rows and the threshold
+    plm_problem_t p = basic_problem(msa, n_seqs, std::max(n_sites, 2), 21);
     p.theta_id = theta_id;
     p.flags = flags & (PLM_FLAG_IGNORE_GAPS | PLM_CONV_MASK);
     PLM_TRY(check_device(0));
     PlmDims d;
     PLM_TRY(make_dims(p, plm_options_from_env(), &d));
+    d.L = n_sites;
     const std::vector<int8_t> rm = padded_rows(d, msa);
     int8_t *dev = nullptr;
     int32_t *cnt = nullptr;

@@ -298,7 +298,8 @@ int plm_reg_parts(const PlmDims &d) { return (int)(d.np_own * d.Q) + (int)((d.nh
 // =========================================================================================
 #define RW_TT 32   // t-rows per register tile
 #define RW_CW 16   // dwords (64 sites) per column chunk
-// zero bytes (gaps) of a packed word -> 0x7c, a value no alignment byte takes (states < 32, pad 127)
+// zero bytes (gaps) of a packed word -> 0x7c, a value no alignment byte takes (states <= 123: plm_reweight_ex refuses
+// 124..126, a context has states < 32; pad 127)
 // 0x80 in every zero byte of v, exactly (all bytes < 0x80: (b & 0x7f) + 0x7f carries into bit 7 iff b != 0, and never
 // into the next byte).  The shorter (v - 0x01010101) & ~v & 0x80808080 is NOT exact per byte: the borrow of a zero byte
 // also flags a byte of value 1 above it -- a residue of state 1 behind a gap would be taken for a gap.

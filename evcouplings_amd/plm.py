@@ -61,7 +61,8 @@ def conventions_from_env(conventions=None):
 
 def reweight(msa, theta_id=0.8, ignore_gaps=False, conventions=0):
     """Cluster sizes (incl. self) at identity >= theta_id; twin of alignment.py:1193-1233.
-    ignore_gaps / conventions: plmc -g semantics and PLM_CONV_* switches."""
+    ignore_gaps / conventions: plmc -g semantics and PLM_CONV_* switches.
+    States are 0..123 (PLM_REWEIGHT_MAX_STATE); one column is enough."""
     lib = _lib.load()
     msa = _msa(msa)
     counts = np.zeros(msa.shape[0], dtype=np.int32)

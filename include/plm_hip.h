@@ -220,7 +220,11 @@ int plm_fit_sharded_rccl(const plm_problem_t *problem, plm_result_t *result, int
                          plm_iter_cb iter_cb, void *iter_user, const void *rccl_id);
 
 /* -- fine-grained, host buffers (parity tests) ------------------------------------------- */
-/* plmc sequence reweighting; twin: align/alignment.py:1193-1233.  counts[s] = cluster size. */
+/* plmc sequence reweighting; twin: align/alignment.py:1193-1233.  counts[s] = cluster size.
+ * States are 0..PLM_REWEIGHT_MAX_STATE (0..123): the compare kernels fill with the bytes 124..127 (a lane's own gaps
+ * under -g, the words past the end of a row, padded columns and rows) and count on no alignment byte having such a
+ * value; an alignment that holds one is refused with PLM_EINVAL, the message names the value and the limit. */
+#define PLM_REWEIGHT_MAX_STATE 123
 int plm_reweight(const int8_t *msa, int32_t n_seqs, int32_t n_sites, double theta_id,
                  int32_t *counts_out);
 /* the same with plmc -g semantics and / or PLM_CONV_* switches: flags = PLM_FLAG_IGNORE_GAPS | PLM_CONV_... */
