@@ -249,6 +249,14 @@ class PlmRbmFitResult(C.Structure):
                 ("trace", C.c_void_p), ("phase_ms", C.c_void_p), ("epochs_done", C.c_int32), ("status", C.c_int32)]
 
 
+class PlmRbmAisResult(C.Structure):
+    _fields_ = [
+        ("log_z", C.c_double), ("log_z0", C.c_double), ("log_z_se", C.c_double), ("ess", C.c_double),
+        ("log_w", C.c_void_p), ("states", C.c_void_p), ("hidden", C.c_void_p),
+        ("steps_done", C.c_int32), ("status", C.c_int32),
+    ]
+
+
 class PlmCrossOpts(C.Structure):
     _fields_ = [("skip_state", C.c_int32), ("want_best", C.c_int32)]
 
@@ -377,6 +385,8 @@ SYMBOLS = [
     ("plm_rbm_sample", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmRbmSampleOpts), C.c_int, _P, _P, _P]),
     ("plm_rbm_fit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmRbmFitOpts), C.c_int, _P,
                               RBM_EPOCH_CB, _P, C.POINTER(PlmRbmFitResult)]),
+    ("plm_rbm_ais", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(PlmAisOpts), C.c_int, _P, AIS_CB, _P,
+                              C.POINTER(PlmRbmAisResult)]),
     ("plm_cross_energies", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P,
                                      C.POINTER(PlmCrossOpts), C.c_int, _P, _P, _P, _P]),
     ("plm_group_assignment", C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P]),

@@ -193,22 +193,6 @@ int plm_ais(int32_t n_sites, int32_t n_states, const float *x_canonical, const p
         result->log_z = result->log_z_se = result->ess = NAN;
         return PLM_OK;
     }
-    // log Z = log Z_0 + log mean w, the sums in chain order in float64
-    double m = logw[0], s1 = 0.0, s2 = 0.0;
-    for (int c = 1; c < C; c++) m = std::max(m, logw[c]);
-    for (int c = 0; c < C; c++) {
-        const double w = exp(logw[c] - m);
-        s1 += w;
-        s2 += w * w;
-    }
-    const double mean = s1 / C;
-    result->log_z = log_z0 + m + log(mean);
-    result->ess = s1 * s1 / s2;
-    double var = 0.0;
-    for (int c = 0; c < C; c++) {
-        const double d = exp(logw[c] - m) - mean;
-        var += d * d;
-    }
-    result->log_z_se = C > 1 ? sqrt(var / (C - 1)) / (sqrt((double)C) * mean) : 0.0;
+    plm_ais_summary(logw.data(), C, log_z0, &result->log_z, &result->log_z_se, &result->ess);
     return PLM_OK;
 }

@@ -93,6 +93,28 @@ inline double plm_n_canon(int L, int q) { return (double)L * q + (double)L * (L 
 
 inline uint32_t plm_state_mask(int q) { return q == 32 ? 0xFFFFFFFFu : (1u << q) - 1u; }   // states 0 .. q-1
 
+// What plm_ais and plm_rbm_ais return from the C log weights of their chains: log Z = log Z_0 + m + log mean w with
+// w = exp(log w - m), m = max log w, the sums in chain order in float64; ess = (sum w)^2 / sum w^2; the standard error
+// of log Z = std(w, ddof = 1) / (sqrt(C) mean w), 0 for C = 1.
+inline void plm_ais_summary(const double *logw, int C, double log_z0, double *log_z, double *log_z_se, double *ess) {
+    double m = logw[0], s1 = 0.0, s2 = 0.0;
+    for (int c = 1; c < C; c++) m = std::max(m, logw[c]);
+    for (int c = 0; c < C; c++) {
+        const double w = exp(logw[c] - m);
+        s1 += w;
+        s2 += w * w;
+    }
+    const double mean = s1 / C;
+    *log_z = log_z0 + m + log(mean);
+    *ess = s1 * s1 / s2;
+    double var = 0.0;
+    for (int c = 0; c < C; c++) {
+        const double d = exp(logw[c] - m) - mean;
+        var += d * d;
+    }
+    *log_z_se = C > 1 ? sqrt(var / (C - 1)) / (sqrt((double)C) * mean) : 0.0;
+}
+
 // The fixed-point weights of the alignment statistics (include/plm_hip.h, three-site section): e = the largest integer
 // <= 30 with max(w) 2^e <= 2^30, wq_n = llrint((double)w_n 2^e), W = sum wq_n.  wq: `padded` entries (>= N, the rest 0);
 // weights == NULL: wq is left empty (every weight is 1) and W = N.  PLM_EINVAL for a weight that is negative or not

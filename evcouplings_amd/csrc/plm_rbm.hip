@@ -1,8 +1,9 @@
 // plm_rbm.hip -- a restricted Boltzmann machine with Potts visible units and Bernoulli hidden units (DESIGN_NEXT_ROWS.md
 // section 9.22; Tubiana, Cocco, Monasson 2019):
 //     I_mu(v) = c_mu + sum_i W_mu,i(v_i),   P(v, h) ~ exp( sum_i g_i(v_i) + sum_mu h_mu I_mu(v) )
-// the score with the hidden-unit inputs (plm_rbm_score), block Gibbs sampling (plm_rbm_sample) and persistent
-// contrastive divergence (plm_rbm_fit).  The parameters are one float32 vector, g [L][q], c [M], W [M][L][q].
+// the score with the hidden-unit inputs (plm_rbm_score), block Gibbs sampling (plm_rbm_sample), persistent
+// contrastive divergence (plm_rbm_fit) and log Z by annealed importance sampling (plm_rbm_ais, section 9.25).  The
+// parameters are one float32 vector, g [L][q], c [M], W [M][L][q].
 //
 // W is expanded once per call or epoch (k_rbm_expand) into the two layouts the kernels read:
 //   Wt [L q][Mp]      one (i, v_i) is one row of M floats (Mp = M rounded up to 8): the gather of the hidden inputs
@@ -321,6 +322,171 @@ __global__ __launch_bounds__(512) void k_rbm_steps(const float4 *__restrict__ G4
         }
 }
 
+// ---- annealed importance sampling (section 9.25) ----------------------------------------------------------------------
+// The products and sums the contract states with one rounding each: the pragma keeps the compiler from fusing them into
+// one multiply-add (see field_plus_scaled of plm_tempered_device.h).
+__device__ __forceinline__ double rbm_scaled_input(float beta, double I) {
+#pragma clang fp contract(off)
+    return (double)beta * I;
+}
+__device__ __forceinline__ float rbm_tempered_arg(float g, float beta, float S) {
+#pragma clang fp contract(off)
+    const float p = beta * S;
+    return g + p;
+}
+// sum + (sp(x1) - sp(x0)), sp(x) = fmax(x, 0) + log1p(e) with e = exp(-|x|) from the caller
+__device__ __forceinline__ double rbm_weight_add(double sum, double x1, double e1, double x0, double e0) {
+#pragma clang fp contract(off)
+    const double s1 = fmax(x1, 0.0) + log1p(e1);
+    const double s0 = fmax(x0, 0.0) + log1p(e0);
+    const double term = s1 - s0;
+    return sum + term;
+}
+// rbm_sigmoid(x) from e = exp(-|x|): on either of its branches that is the exponential rbm_sigmoid takes, of the same
+// argument, so the value is the same
+__device__ __forceinline__ double rbm_sigmoid_from(double x, double e) {
+    return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+
+// The steps [k0, k1) of the anneal on the tile of k_rbm_steps (lanes are chains, NW waves share the hidden chunks and then
+// the sites), with the inverse temperature betas[k + 1] on the hidden layer: the inputs of a chunk of RBM_HB hidden units
+// in float64, x = beta I, the draw on sigma(x), and on the first sweep of a step the chunk's sum of
+// softplus(beta_k I) - softplus(beta_{k-1} I) into ws[chunk][lane] (LDS, behind the hidden bits).  After the barrier
+// between the halves wave 0 adds the chunk sums in chunk order into log w, which it holds in a register: the order is
+// the shape's, whatever NW.  first != 0: the start rule and log w = 0; otherwise states and log w are read, and both are
+// written back.  hid (or null) [C][M]: the hidden units of the launch's last sweep.
+template <int NV>
+__global__ __launch_bounds__(512) void k_rbm_ais(const float4 *__restrict__ G4, const float *__restrict__ c,
+                                                 const float *__restrict__ Wt, const float4 *__restrict__ Wv4, int L, int q,
+                                                 int M, int Mp, int C, const float *__restrict__ betas /* [K + 1] */,
+                                                 int k0, int k1, int n_per, int first, uint32_t allowed, uint32_t seed_lo,
+                                                 uint32_t seed_hi, int8_t *states /* [C][L] */,
+                                                 double *logw_io /* [C] */, int8_t *__restrict__ hid) {
+    extern __shared__ uint32_t rbm_lds[];
+    constexpr int TILE = 64;
+    const int tid = threadIdx.x & 63, wave = threadIdx.x >> 6, NW = blockDim.x >> 6, n_thr = blockDim.x;
+    const int L4 = (L + 3) >> 2, MB = (M + RBM_HB - 1) / RBM_HB, MW = (MB + 3) >> 2;
+    uint32_t *xw = rbm_lds, *hw = rbm_lds + L4 * TILE;
+    uint8_t *xs = (uint8_t *)xw, *hb = (uint8_t *)hw;
+    double *ws = (double *)(rbm_lds + (L4 + MW) * TILE);      // [MB][TILE]; (L4 + MW) 256 bytes in: aligned
+    const int c0 = blockIdx.x * TILE;
+    const int n_here = min(TILE, C - c0);
+    const uint32_t chain = (uint32_t)(c0 + tid);
+    for (int k = threadIdx.x; k < (L4 + MW) * TILE; k += n_thr) rbm_lds[k] = 0u;
+    __syncthreads();
+    if (first) {
+        for (int i = wave; i < L; i += NW) {
+            float4 U[NV];
+#pragma unroll
+            for (int v = 0; v < NV; v++) U[v] = G4[i * NV + v];
+            xs[RBM_XS(i, tid)] = (uint8_t)draw_state<NV>(U, q, allowed, 1.0f,
+                                                          philox_word0(chain, 0u, GS_START_SWEEP, (uint32_t)i, seed_lo, seed_hi));
+        }
+    } else {
+        for (int k = threadIdx.x; k < n_here * L; k += n_thr) {
+            const int cl = k / L, j = k - cl * L;
+            xs[RBM_XS(j, cl)] = (uint8_t)states[(int64_t)c0 * L + k];
+        }
+    }
+    const bool keeps_w = wave == 0 && tid < n_here;
+    double logw = (!first && keeps_w) ? logw_io[c0 + tid] : 0.0;
+    __syncthreads();
+    for (int k = k0; k < k1; k++) {
+        const float beta = betas[k + 1], beta_prev = betas[k];
+        for (int s = 0; s < n_per; s++) {
+            const uint32_t sweep = (uint32_t)k * (uint32_t)n_per + (uint32_t)s;
+            const bool weigh = s == 0;
+            for (int ch = wave; ch < MB; ch += NW) {
+                const int m0 = ch * RBM_HB;
+                double I[RBM_HB];
+#pragma unroll
+                for (int k8 = 0; k8 < RBM_HB; k8++) I[k8] = m0 + k8 < M ? (double)c[m0 + k8] : 0.0;
+                const float *base = Wt + m0;
+                for (int i4 = 0; i4 < L4; i4++) {
+                    const uint32_t word = xw[i4 * TILE + tid];
+#pragma unroll
+                    for (int k4 = 0; k4 < 4; k4++) {
+                        const int i = 4 * i4 + k4;
+                        if (i < L) {
+                            const int xi = (word >> (8 * k4)) & 0xff;
+                            const float4 *row = (const float4 *)(base + ((int64_t)i * q + xi) * Mp);
+                            const float4 r0 = row[0], r1 = row[1];
+                            I[0] += (double)r0.x; I[1] += (double)r0.y; I[2] += (double)r0.z; I[3] += (double)r0.w;
+                            I[4] += (double)r1.x; I[5] += (double)r1.y; I[6] += (double)r1.z; I[7] += (double)r1.w;
+                        }
+                    }
+                }
+                uint32_t bits = 0u;
+                double wsum = 0.0;
+#pragma unroll
+                for (int k8 = 0; k8 < RBM_HB; k8++) {
+                    if (m0 + k8 < M) {
+                        const double x = rbm_scaled_input(beta, I[k8]);
+                        const double e = exp(-fabs(x));
+                        if (weigh) {
+                            const double x0 = rbm_scaled_input(beta_prev, I[k8]);
+                            wsum = rbm_weight_add(wsum, x, e, x0, exp(-fabs(x0)));
+                        }
+                        const double p = rbm_sigmoid_from(x, e);
+                        const float u = uniform24(philox_word0(chain, 2u, sweep, (uint32_t)(m0 + k8), seed_lo, seed_hi));
+                        if ((double)u < p) bits |= 1u << k8;
+                    }
+                }
+                hb[RBM_XS(ch, tid)] = (uint8_t)bits;
+                if (weigh) ws[ch * TILE + tid] = wsum;
+            }
+            __syncthreads();
+            if (weigh && wave == 0) {                 // ws is next written behind the barrier that ends this sweep
+                double t = 0.0;
+                for (int ch = 0; ch < MB; ch++) t += ws[ch * TILE + tid];
+                logw += t;
+            }
+            for (int i = wave; i < L; i += NW) {
+                float4 S[NV];
+#pragma unroll
+                for (int v = 0; v < NV; v++) S[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int w = 0; w < MW; w++) {
+                    const uint32_t bits = hw[w * TILE + tid];
+                    const int kmax = min(32, M - 32 * w);
+                    for (int kb = 0; kb < kmax; kb++) {
+                        const bool on = (bits >> kb) & 1u;
+                        const float4 *row = Wv4 + ((int64_t)(32 * w + kb) * L + i) * NV;
+#pragma unroll
+                        for (int v = 0; v < NV; v++) {
+                            const float4 r = row[v];
+                            S[v].x = on ? S[v].x + r.x : S[v].x;
+                            S[v].y = on ? S[v].y + r.y : S[v].y;
+                            S[v].z = on ? S[v].z + r.z : S[v].z;
+                            S[v].w = on ? S[v].w + r.w : S[v].w;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int v = 0; v < NV; v++) {
+                    const float4 gv = G4[i * NV + v];
+                    S[v].x = rbm_tempered_arg(gv.x, beta, S[v].x);
+                    S[v].y = rbm_tempered_arg(gv.y, beta, S[v].y);
+                    S[v].z = rbm_tempered_arg(gv.z, beta, S[v].z);
+                    S[v].w = rbm_tempered_arg(gv.w, beta, S[v].w);
+                }
+                xs[RBM_XS(i, tid)] = (uint8_t)draw_state<NV>(S, q, allowed, 1.0f,
+                                                              philox_word0(chain, 0u, sweep, (uint32_t)i, seed_lo, seed_hi));
+            }
+            __syncthreads();
+        }
+    }
+    for (int k = threadIdx.x; k < n_here * L; k += n_thr) {
+        const int cl = k / L, j = k - cl * L;
+        states[(int64_t)c0 * L + k] = (int8_t)xs[RBM_XS(j, cl)];
+    }
+    if (keeps_w) logw_io[c0 + tid] = logw;
+    if (hid)
+        for (int k = threadIdx.x; k < n_here * M; k += n_thr) {
+            const int cl = k / M, mu = k - cl * M;
+            hid[(int64_t)c0 * M + k] = (int8_t)((hw[(mu >> 5) * TILE + cl] >> (mu & 31)) & 1u);
+        }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 int rbm_check_shape(int L, int q, int M, const char *who) {
     if (L < 1 || M < 1) return plm_fail(PLM_EINVAL, "%s: need n_sites >= 1 and n_hidden >= 1 (got %d, %d)", who, L, M);
@@ -381,9 +547,17 @@ struct RbmPlan {
     size_t lds = 0;
 };
 size_t rbm_lds_bytes(int L, int M) { return (size_t)((L + 3) / 4 + (M + 31) / 32) * 64 * 4; }
-int rbm_plan(int L, int M, int C, int device, RbmPlan *out) {
-    if (rbm_lds_bytes(L, M) > GS_LDS_BYTES)
+// with the chunk sums ws[M / 8][64] of k_rbm_ais behind them
+size_t rbm_ais_lds_bytes(int L, int M) { return rbm_lds_bytes(L, M) + (size_t)((M + RBM_HB - 1) / RBM_HB) * 64 * sizeof(double); }
+int rbm_check_lds(int L, int M, size_t lds) {
+    if (lds > GS_LDS_BYTES)
         return plm_fail(PLM_EUNSUPPORTED, "%d sites and %d hidden units: the states of 64 chains do not fit the LDS of a CU", L, M);
+    return PLM_OK;
+}
+// lds: the bytes of a tile (0: those of k_rbm_steps)
+int rbm_plan(int L, int M, int C, int device, RbmPlan *out, size_t lds = 0) {
+    if (lds == 0) lds = rbm_lds_bytes(L, M);
+    PLM_TRY(rbm_check_lds(L, M, lds));
     const char *forced = getenv("PLM_RBM_WAVES");
     int waves = 1;
     if (forced && *forced) {
@@ -397,7 +571,7 @@ int rbm_plan(int L, int M, int C, int device, RbmPlan *out) {
         while (waves < 8 && tiles * waves < 16 * (int64_t)prop.multiProcessorCount) waves *= 2;
     }
     out->waves = waves;
-    out->lds = rbm_lds_bytes(L, M);
+    out->lds = lds;
     return PLM_OK;
 }
 
@@ -424,6 +598,40 @@ hipError_t rbm_steps(const RbmModel &m, const RbmPlan &p, hipStream_t st, int C,
     }
 #undef RBM_STEPS_CASE
     return hipGetLastError();
+}
+
+// the steps [k0, k1) of the anneal in one launch of k_rbm_ais, under a plan made with rbm_ais_lds_bytes
+hipError_t rbm_ais_steps(const RbmModel &m, const RbmPlan &p, hipStream_t st, int C, const float *betas, int k0, int k1,
+                         int n_per, uint64_t seed, int8_t *states, double *logw, int8_t *hid) {
+    const gibbs::Seed sd(seed);
+    const dim3 grid((unsigned)((C + 63) / 64));
+    const uint32_t allowed = plm_state_mask(m.q);
+    hipError_t e = hipSuccess;
+#define RBM_AIS_CASE(NV_)                                                                                              \
+    case NV_:                                                                                                          \
+        e = hipFuncSetAttribute((const void *)k_rbm_ais<NV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds); \
+        if (e != hipSuccess) return e;                                                                                 \
+        hipLaunchKernelGGL(k_rbm_ais<NV_>, grid, dim3(64 * p.waves), p.lds, st, (const float4 *)m.Gp, m.c(), m.Wt,     \
+                           (const float4 *)m.Wv, m.L, m.q, m.M, m.Mp, C, betas, k0, k1, n_per, k0 == 0 ? 1 : 0, allowed, \
+                           sd.lo, sd.hi, states, logw, hid);                                                           \
+        break;
+    switch (m.NV) {
+        RBM_AIS_CASE(1) RBM_AIS_CASE(2) RBM_AIS_CASE(3) RBM_AIS_CASE(4)
+        RBM_AIS_CASE(5) RBM_AIS_CASE(6) RBM_AIS_CASE(7) RBM_AIS_CASE(8)
+    default: return hipErrorInvalidValue;
+    }
+#undef RBM_AIS_CASE
+    return hipGetLastError();
+}
+
+// Steps of n_per sweeps per launch, out of K, that keep a launch of plm_rbm_ais near a second.  An estimate, not a
+// measurement of this kernel: the 10.2 ms block-Gibbs step of section 9.22 (65 536 chains, L = 300, M = 128, NV = 6, four
+// tiles per CU) scaled in proportion to M L NV and the tiles per CU.
+int rbm_ais_steps_per_launch(const RbmModel &m, int C, int n_per, int K, int n_cu) {
+    const double rounds = std::ceil((double)((C + 63) / 64) / std::max(n_cu, 1));
+    const double per_step = (double)n_per * 10.2e-3 * ((double)m.M * m.L * m.NV) / (128.0 * 300.0 * 6.0) * rounds / 4.0;
+    const double steps = 1.0 / std::max(per_step, 1e-9);
+    return steps >= (double)K ? K : std::max(1, (int)steps);
 }
 
 // The statistics of n rows (data or chains) at the expanded model: stat [g | c | W] in float64.
@@ -684,5 +892,93 @@ int plm_rbm_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t
     PLM_HIP(hipStreamSynchronize(st));
     result->epochs_done = done_epochs;
     result->status = status;
+    return PLM_OK;
+}
+
+int plm_rbm_ais(int32_t n_sites, int32_t n_states, int32_t n_hidden, const float *params, const plm_ais_opts *opts,
+                int device, void *stream, plm_ais_cb cb, void *user, plm_rbm_ais_result *result) {
+    if (!opts || !result) return plm_fail(PLM_EINVAL, "plm_rbm_ais: NULL options or result");
+    if (!params) return plm_fail(PLM_EINVAL, "plm_rbm_ais: NULL model");
+    const int L = n_sites, q = n_states, M = n_hidden, C = opts->n_chains, K = opts->n_temps, n = opts->sweeps_per_temp;
+    PLM_TRY(rbm_check_shape(L, q, M, "plm_rbm_ais"));
+    if (C < 1 || K < 1 || n < 1 || opts->steps_per_launch < 0)
+        return plm_fail(PLM_EINVAL, "plm_rbm_ais: need n_chains >= 1, n_temps >= 1, sweeps_per_temp >= 1, steps_per_launch >= 0 "
+                                    "(got %d, %d, %d, %d)", C, K, n, opts->steps_per_launch);
+    if ((double)K * (double)n >= 4294967295.0)
+        return plm_fail(PLM_EINVAL, "plm_rbm_ais: n_temps x sweeps_per_temp must stay below 2^32 - 1 sweeps");
+    if ((double)C * L >= 2147483647.0 || (double)C * M >= 2147483647.0)
+        return plm_fail(PLM_EINVAL, "plm_rbm_ais: n_chains x n_sites and n_chains x n_hidden must stay below 2^31");
+    if (opts->betas) {
+        if (opts->betas[0] != 0.f) return plm_fail(PLM_EINVAL, "plm_rbm_ais: betas[0] must be 0 (got %g)", (double)opts->betas[0]);
+        for (int k = 1; k <= K; k++)
+            if (!std::isfinite(opts->betas[k]) || !(opts->betas[k] >= opts->betas[k - 1]))
+                return plm_fail(PLM_EINVAL, "plm_rbm_ais: betas must be finite and non-decreasing (betas[%d] = %g after %g)", k,
+                                (double)opts->betas[k], (double)opts->betas[k - 1]);
+    }
+    PLM_TRY(rbm_check_lds(L, M, rbm_ais_lds_bytes(L, M)));
+    PLM_TRY(plm_check_device(device));
+    RbmModel m(L, q, M);
+    const size_t CL = (size_t)C * L, CM = (size_t)C * M;
+    PLM_TRY(plm_check_free(m.bytes() + (double)CL + 8.0 * C + (result->hidden ? (double)CM : 0.0) + 4.0 * ((double)K + 1.0),
+                           "plm_rbm_ais"));
+    RbmPlan plan;
+    PLM_TRY(rbm_plan(L, M, C, device, &plan, rbm_ais_lds_bytes(L, M)));
+    int n_cu = 0;
+    PLM_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+    const int per_launch = opts->steps_per_launch > 0 ? std::min(opts->steps_per_launch, K)
+                                                      : rbm_ais_steps_per_launch(m, C, n, K, n_cu);
+
+    // log Z_0 = M log 2 + sum_i log sum_a exp g_i(a) in float64
+    double log_z0 = (double)M * log(2.0);
+    for (int i = 0; i < L; i++) {
+        const float *g = params + (size_t)i * q;
+        double mx = g[0], s = 0.0;
+        for (int a = 1; a < q; a++) mx = std::max(mx, (double)g[a]);
+        for (int a = 0; a < q; a++) s += exp((double)g[a] - mx);
+        log_z0 += mx + log(s);
+    }
+    std::vector<float> betas((size_t)K + 1);
+    for (int k = 0; k <= K; k++) betas[k] = opts->betas ? opts->betas[k] : (float)((double)k / (double)K);
+
+    hipStream_t st = (hipStream_t)stream;
+    DeviceBuffers mem;
+    float *d_betas = nullptr;
+    int8_t *states = nullptr, *hid = nullptr;
+    double *d_logw = nullptr;
+    PLM_TRY(m.alloc(mem));
+    PLM_TRY(mem.alloc(&d_betas, betas.size()));
+    PLM_TRY(mem.alloc(&states, CL));
+    PLM_TRY(mem.alloc(&d_logw, (size_t)C));
+    if (result->hidden) PLM_TRY(mem.alloc(&hid, CM));
+    PLM_HIP(hipMemcpyAsync(m.x, params, sizeof(float) * m.n_par, hipMemcpyHostToDevice, st));
+    PLM_HIP(hipMemcpyAsync(d_betas, betas.data(), betas.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    PLM_HIP(m.expand(st));
+    int steps_done = 0, status = PLM_STATUS_CONVERGED;
+    while (steps_done < K) {
+        const int k1 = std::min(K, steps_done + per_launch);
+        PLM_HIP(rbm_ais_steps(m, plan, st, C, d_betas, steps_done, k1, n, opts->seed, states, d_logw, hid));
+        steps_done = k1;
+        if (cb && steps_done < K) {
+            PLM_HIP(hipStreamSynchronize(st));
+            if (cb((int32_t)steps_done, (int32_t)K, user)) {
+                status = PLM_STATUS_INTERRUPTED;
+                break;
+            }
+        }
+    }
+    std::vector<double> logw((size_t)C);
+    PLM_HIP(hipMemcpyAsync(logw.data(), d_logw, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (result->states) PLM_HIP(hipMemcpyAsync(result->states, states, CL, hipMemcpyDeviceToHost, st));
+    if (result->hidden) PLM_HIP(hipMemcpyAsync(result->hidden, hid, CM, hipMemcpyDeviceToHost, st));
+    PLM_HIP(hipStreamSynchronize(st));
+    if (result->log_w) std::copy(logw.begin(), logw.end(), result->log_w);
+    result->log_z0 = log_z0;
+    result->steps_done = steps_done;
+    result->status = status;
+    if (status == PLM_STATUS_INTERRUPTED) {
+        result->log_z = result->log_z_se = result->ess = NAN;
+        return PLM_OK;
+    }
+    plm_ais_summary(logw.data(), C, log_z0, &result->log_z, &result->log_z_se, &result->ess);
     return PLM_OK;
 }

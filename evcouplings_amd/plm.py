@@ -691,6 +691,48 @@ def rbm_fit(msa, weights, q, g, c, W, n_chains, n_epochs, steps_per_epoch=2, lr=
     return out
 
 
+def rbm_log_partition(g, c, W, q, n_chains=4096, n_temps=1000, sweeps_per_temp=1, betas=None, seed=0, steps_per_launch=0,
+                      callback=None, hidden=False, device=0):
+    """
+    log Z of the restricted Boltzmann machine (g, c, W) by annealed importance sampling on the GPU (plm_rbm_ais,
+    DESIGN_NEXT_ROWS.md section 9.25): n_chains chains are annealed from the independent-site model of g (log Z_0 in
+    closed form) to the full model over n_temps steps of sweeps_per_temp block-Gibbs sweeps each, with the inverse
+    temperature beta_k on the hidden layer only (c and W scaled by it).  betas, steps_per_launch and callback are those
+    of `log_partition`; with betas the result is log Z of the model with c and W scaled by beta_K.
+    Returns a dict: log_z, log_z0, log_z_se, ess, log_w [C], states int8 [C, L], with hidden also hidden int8 [C, M] (the
+    hidden units of the last sweep), steps_done, status ("converged" or "interrupted": log_z is NaN then).  When
+    beta_K = 1 and the run completed also mean_score = sum_c w_c score(v_c) over the normalised weights, the score from
+    `rbm_score` on the final states, and entropy = log_z - mean_score.
+    """
+    q, C_ = int(q), int(n_chains)
+    x, L, M = _rbm_model(g, c, W, q)
+    if betas is not None:
+        betas = np.ascontiguousarray(betas, dtype=np.float32).reshape(-1)
+        if betas.size < 2:
+            raise ValueError("betas must hold at least beta_0 and beta_1")
+        K = betas.size - 1
+    else:
+        K = int(n_temps)
+    opts = _lib.PlmAisOpts(C_, K, int(sweeps_per_temp), int(steps_per_launch), _ptr(betas), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    n_out = max(C_, 1)
+    log_w, states = np.zeros(n_out), np.zeros((n_out, L), np.int8)
+    hid = np.zeros((n_out, M), np.int8) if hidden else None
+    res = _lib.PlmRbmAisResult(0.0, 0.0, 0.0, 0.0, _ptr(log_w), _ptr(states), _ptr(hid), 0, 0)
+    cb, reraise = _stop_callback(_lib.AIS_CB, callback)
+    check(_lib.load().plm_rbm_ais(L, q, M, _ptr(x), C.byref(opts), int(device), None, cb, None, C.byref(res)))
+    reraise()
+    out = dict(log_z=float(res.log_z), log_z0=float(res.log_z0), log_z_se=float(res.log_z_se), ess=float(res.ess),
+               log_w=log_w, states=states, steps_done=int(res.steps_done), status=BM_STATUS[int(res.status)])
+    if hidden:
+        out["hidden"] = hid
+    last = 1.0 if betas is None else float(betas[-1])
+    if res.status == _lib.STATUS_CONVERGED and last == 1.0:
+        w = np.exp(log_w - log_w.max())
+        out["mean_score"] = float((w / w.sum()) @ rbm_score(states, q, g, c, W, device=device))
+        out["entropy"] = out["log_z"] - out["mean_score"]
+    return out
+
+
 def sample_plan(L, q, n_chains, n_cu=0):
     """
     The launch plan `sample` and `bm_fit` use for L sites, q states and n_chains chains (plm_sample_plan,

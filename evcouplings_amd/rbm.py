@@ -8,9 +8,14 @@ visible units at the L sites, M Bernoulli hidden units,
                                       [--steps K] [--lr X] [--lr-decay-after T] [--lambda-g X] [--lambda-w X] [--seed S]
     python -m evcouplings_amd.rbm sample MODEL.npz -n N -o OUT.a2m [--burn-in B] [--no-gaps] [--seed S]
     python -m evcouplings_amd.rbm score MODEL.npz --sequences IN.a2m -o OUT.csv [--features FEATURES.npy]
+                                        [--log-z VALUE|ais]
+    python -m evcouplings_amd.rbm logz MODEL.npz [-n CHAINS] [-k TEMPS] [--sweeps N] [--seed S]
 
-`score` writes log P(v) + log Z: scores of one model compare, scores of two models do not (log Z is only computed by
-`log_partition_exact`, for small M).  `--features` saves the hidden-unit inputs I [n, M], the per-sequence feature vector.
+`score` writes log P(v) + log Z: scores of one model compare, scores of two models do not.  `--log-z` adds the column
+log_prob = score - log Z, with the value given or with the estimate of `logz` at its defaults ("ais").  `logz` estimates
+log Z by annealed importance sampling (plm.rbm_log_partition, DESIGN_NEXT_ROWS.md section 9.25) and prints it with its
+standard error, the effective sample size, log Z_0 and the entropy.  `--features` saves the hidden-unit inputs I [n, M],
+the per-sequence feature vector.
 
 The file is an .npz with kind="rbm".  The fit is persistent contrastive divergence by plain gradient ascent (plm.rbm_fit).
 The defaults (64 hidden units, 1000 chains, 200 epochs of 2 steps, lr 0.1, lambda_w = 1e-3, the pseudo-count of the
@@ -143,6 +148,32 @@ def log_partition_exact(model):
     return float(t + np.log(np.exp(terms - t).sum()))
 
 
+def log_partition(model, **kw):
+    """
+    log Z by annealed importance sampling (plm.rbm_log_partition, whose keyword arguments these are: n_chains, n_temps,
+    sweeps_per_temp, betas, seed, ...): its dict, with log_z, log_z_se, ess, log_z0 and, when the anneal ends at beta = 1,
+    mean_score and entropy.  For any number of hidden units; log_partition_exact is the check for small ones.
+    """
+    return plm.rbm_log_partition(model.g, model.c, model.W, model.q, **kw)
+
+
+def log_probabilities(model, seqs, log_z=None, **kw):
+    """
+    (log P(v) of (n, L) states, the dict of log_partition): the scores minus log_z.  log_z None: the anneal is run with
+    the keyword arguments of log_partition; a given log_z is used as it is, and the dict holds it alone.
+    """
+    device = kw.get("device", 0)
+    res = log_partition(model, **kw) if log_z is None else dict(log_z=float(log_z))
+    return scores(model, seqs, device=device) - res["log_z"], res
+
+
+def mean_log_likelihood(model, msa, weights=None, log_z=None, **kw):
+    """the weighted mean of log P over the rows of msa (weights None: every row counts once)"""
+    lp, _ = log_probabilities(model, msa, log_z, **kw)
+    w = np.ones(len(lp)) if weights is None else np.asarray(weights, np.float64)
+    return float((w * lp).sum() / w.sum())
+
+
 def save(path, model):
     with open(path, "wb") as f:
         np.savez(f, kind="rbm", **{k: getattr(model, k) for k in FIELDS})
@@ -201,6 +232,13 @@ def main(argv=None):
     c.add_argument("--sequences", required=True)
     c.add_argument("-o", required=True)
     c.add_argument("--features", default=None, help="save the hidden-unit inputs [n, M] to this .npy file")
+    c.add_argument("--log-z", default=None, metavar="VALUE|ais", help="add the column log_prob = score - log Z")
+    z = sub.add_parser("logz")
+    z.add_argument("model")
+    z.add_argument("-n", type=int, default=4096, help="chains")
+    z.add_argument("-k", type=int, default=1000, help="temperatures")
+    z.add_argument("--sweeps", type=int, default=1)
+    z.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
     if a.cmd == "fit":
         enc = alignment_io.encode_alignment(a.alignment, focus_seq=a.focus)
@@ -219,15 +257,27 @@ def main(argv=None):
         x = sample_sequences(model, a.n, burn_in=a.burn_in, seed=a.seed, exclude=model.alphabet[0] if a.no_gaps else "")
         write_a2m(a.o, model, _letters(model, x))
         return 0
+    if a.cmd == "logz":
+        r = log_partition(model, n_chains=a.n, n_temps=a.k, sweeps_per_temp=a.sweeps, seed=a.seed)
+        print("log Z = %.6f +- %.6f (ESS = %.1f of %d chains, %d temperatures x %d sweeps)"
+              % (r["log_z"], r["log_z_se"], r["ess"], a.n, a.k, a.sweeps))
+        print("log Z_0 = %.6f, entropy = %.6f" % (r["log_z0"], r["entropy"]))
+        return 0
     enc = alignment_io.encode_alignment(a.sequences, alphabet=model.alphabet)
     if enc.msa.shape[1] != model.L:
         ap.error("%s has %d columns, the model %d sites" % (a.sequences, enc.msa.shape[1], model.L))
     sc, feats = plm.rbm_score(enc.msa, model.q, model.g, model.c, model.W, inputs=True)
     ids = [h for h, ok in zip(enc.ids, enc.valid) if ok]
+    log_z = None
+    if a.log_z is not None:
+        log_z = log_partition(model)["log_z"] if a.log_z == "ais" else float(a.log_z)
     with open(a.o, "w") as out:
-        out.write("id,score\n")
+        out.write("id,score,log_prob\n" if log_z is not None else "id,score\n")
         for h, v in zip(ids, sc):
-            out.write("%s,%.17g\n" % (h.split()[0], v))
+            if log_z is not None:
+                out.write("%s,%.17g,%.17g\n" % (h.split()[0], v, v - log_z))
+            else:
+                out.write("%s,%.17g\n" % (h.split()[0], v))
     if a.features:
         np.save(a.features, feats)
     return 0

@@ -1113,7 +1113,7 @@ int plm_ar_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t 
  * q in 2..32 (PLM_EUNSUPPORTED otherwise), L >= 1, M >= 1, M L q below 2^31 (and M at most 64 x 65535, else
  * PLM_EUNSUPPORTED).  In all three calls the arguments are checked before the device is looked at (PLM_EINVAL: NULL
  * arguments, sizes below 1, rows x L at or above 2^31, states outside 0..q-1 and what each call names below), and
- * PLM_ENOMEM is decided before any allocation.  log Z is not computed here.
+ * PLM_ENOMEM is decided before any allocation.  log Z is not computed here (plm_rbm_ais, below, estimates it).
  *
  * plm_rbm_score: score_out [n] and inputs_out [n][M] (or NULL), float64.  I_mu is accumulated in float64 from (double) c_mu,
  *   then one add per site i = 0 .. L-1 in that order of (double) W_mu,i(v_i); softplus(I) = max(I, 0) + log1p(exp(-|I|));
@@ -1207,6 +1207,50 @@ int plm_rbm_sample(int32_t n_sites, int32_t n_states, int32_t n_hidden, const fl
 int plm_rbm_fit(const int8_t *msa, const float *weights, int32_t n_seqs, int32_t n_sites, int32_t n_states, int32_t n_hidden,
                 const float *x_start, const plm_rbm_fit_opts *opts, int device, void *stream, plm_rbm_epoch_cb cb, void *user,
                 plm_rbm_fit_result *result);
+
+/* ---- log Z of the restricted Boltzmann machine by annealed importance sampling (DESIGN_NEXT_ROWS.md section 9.25) ------
+ * The model is the RBM above (g [L][q], c [M], W [M][L][q] in the RBM layout, q in 2..32).  The path puts the inverse
+ * temperature on the hidden layer only, as plm_ais puts it on the couplings only:
+ *     p*_beta(v) = exp( sum_i g_i(v_i) ) prod_mu (1 + exp(beta I_mu(v))),    I_mu(v) = c_mu + sum_i W_mu,i(v_i)
+ * beta = 0 is the independent-site model of g, sampled exactly, with log_z0 = M log 2 + sum_i log sum_a exp g_i(a) in
+ * float64 on the host.  The schedule is that of plm_ais: K + 1 float32 values beta_0 = 0 <= ... <= beta_K, all finite;
+ * betas == NULL: beta_k = (float)((double)k / K).  beta_K need not be 1: the result is log Z of the model with c and W
+ * scaled by beta_K, so every prefix of a schedule is a schedule.  plm_ais_opts and plm_ais_cb mean here what they mean
+ * for plm_ais.
+ * Start: chain c begins from plm_rbm_sample's start rule on g (all states allowed, counter (c, 0, 0xFFFFFFFF, i)) with
+ * log w = 0.  Step k = 1 .. K on the current states v:
+ *   1. inputs: I_mu = (double)c_mu, then one float64 add per site i = 0 .. L-1 of (double)W_mu,i(v_i): the bits
+ *      plm_rbm_score returns in inputs_out
+ *   2. weight, on the first sweep of the step only: x_k = (double)beta_k I_mu and x_{k-1} = (double)beta_{k-1} I_mu, one
+ *      product each; sp(x) = fmax(x, 0) + log1p(exp(-fabs(x))); term_mu = sp(x_k) - sp(x_{k-1}).  The terms are summed
+ *      from 0.0 in mu order inside each chunk of 8 hidden units (mu = 8 j .. 8 j + 7), the chunk sums are added from 0.0
+ *      in chunk order, and that sum is added to log w.  No product is fused with a sum.
+ *   3. n = sweeps_per_temp sweeps with the sweep indices (k-1) n .. k n - 1; every sweep after the first recomputes I from
+ *      the current states.
+ *      hidden half: p_mu = sigma(x_k) in float64 (1 / (1 + exp(-x)) for x >= 0, else e / (1 + e) with e = exp(x));
+ *        h_mu = ((double)u < p_mu), u the float32 uniform ((word0 >> 8) + 0.5) 2^-24 (kept below 1) of the counter
+ *        (c, 2, sweep, mu)
+ *      visible half, every site: S_a starts at 0.0f and adds W_mu,i(a) in float32 for every set h_mu in mu order;
+ *        arg_a = fadd(g_i(a), fmul(beta_k, S_a)), two roundings; the draw of plm_sample's contract on arg at beta = 1
+ *        with the counter (c, 0, sweep, i)
+ * log_z, log_z_se and ess are formed from log w as plm_ais forms them.  log w, the states and the hidden units of chain c
+ * depend on (seed, c, model, schedule, n) only: not on C, on the waves that share a tile (PLM_RBM_WAVES) or on how the
+ * steps are cut into launches (steps_per_launch; 0: about a second each).  cb, if given, is called between launches and
+ * cancels by returning non-zero: PLM_STATUS_INTERRUPTED, the three summaries NaN, the arrays of the steps_done steps that
+ * ran.  Before the device is looked at: PLM_EINVAL for NULL opts, result or params, the shape checks of plm_rbm_score,
+ * C, K or n below 1, steps_per_launch below 0, K n >= 2^32 - 1, C L or C M at or above 2^31 and the schedule checks of
+ * plm_ais; PLM_EUNSUPPORTED for q outside 2..32 and when the tile of 64 chains (L / 4 + M / 32 words and M / 8 doubles
+ * per chain) does not fit the LDS of a CU.  PLM_ENOMEM is decided before any array but the schedule is read. */
+typedef struct {
+    double log_z, log_z0, log_z_se, ess;
+    double *log_w;             /* [C] or NULL                                                          */
+    int8_t *states;            /* C x L final states, or NULL                                          */
+    int8_t *hidden;            /* C x M hidden units of the last sweep, or NULL                        */
+    int32_t steps_done;
+    int32_t status;            /* PLM_STATUS_CONVERGED when all K steps ran, else PLM_STATUS_INTERRUPTED */
+} plm_rbm_ais_result;
+int plm_rbm_ais(int32_t n_sites, int32_t n_states, int32_t n_hidden, const float *params, const plm_ais_opts *opts,
+                int device, void *stream, plm_ais_cb cb, void *user, plm_rbm_ais_result *result);
 
 /* ---- inter-protein coupling energies of two sequence sets, and matching by them (DESIGN_NEXT_ROWS.md section 9.23) ----
  * For a row s of A (n_sites_a states) and a row t of B (n_sites_b states) of the same group
